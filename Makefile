@@ -48,10 +48,14 @@ clean:
 # toolchain (prototypes declared by internal.h under the forced gate; the
 # objects are NOT linked into the library).  On a real MPI-4 library the
 # gate turns on automatically — see internal.h.
+# The scratch objects stay in-tree (build/ is ignored): a fixed name in a
+# shared temp directory cannot be overwritten once another user has made it.
+MPI4CHECK_DIR := build/mpi4check
 mpi4check:
-	$(HIPCC) $(CXXFLAGS) -DMPIX_MPI_PARTITIONED -c src/partitioned.cpp -o /tmp/mpix_p4_part.o
-	$(HIPCC) $(CXXFLAGS) -DMPIX_MPI_PARTITIONED -c src/transport/mpi.cpp -o /tmp/mpix_p4_mpi.o
-	$(HIPCC) $(CXXFLAGS) -DMPIX_MPI_PARTITIONED -c src/enqueue.cpp -o /tmp/mpix_p4_enq.o
+	mkdir -p $(MPI4CHECK_DIR)
+	$(HIPCC) $(CXXFLAGS) -DMPIX_MPI_PARTITIONED -c src/partitioned.cpp -o $(MPI4CHECK_DIR)/part.o
+	$(HIPCC) $(CXXFLAGS) -DMPIX_MPI_PARTITIONED -c src/transport/mpi.cpp -o $(MPI4CHECK_DIR)/mpi.o
+	$(HIPCC) $(CXXFLAGS) -DMPIX_MPI_PARTITIONED -c src/enqueue.cpp -o $(MPI4CHECK_DIR)/enq.o
 	@echo "mpi4check: MPI-4 partitioned passthrough compiles both ways"
 
 .PHONY: all clean python mpi4check

@@ -24,7 +24,7 @@ step smoke 120 python -c 'from __graft_entry__ import smoke; smoke()'
 # headline stability: 5 back-to-back repetitions -> median +- spread
 note bench_repeat
 for i in 1 2 3 4 5; do
-    timeout 150 python bench.py --steps 20 --warmup 5 \
+    timeout 150 python bench.py --full --steps 20 --warmup 5 \
         > "gpurun_out/bench_rep$i.log" 2>&1 \
         && tail -1 "gpurun_out/bench_rep$i.log" || echo "rep$i FAIL rc=$?"
 done
@@ -82,7 +82,7 @@ if [ "$MODE" = full ]; then
     note rocprof
     ( cd /tmp && timeout 150 rocprofv3 --kernel-trace --stats \
         -d "$OLDPWD/gpurun_out/prof" -o ci \
-        -- python "$OLDPWD/bench.py" --steps 5 --warmup 2 --msg-mib 64 \
+        -- python "$OLDPWD/bench.py" --full --steps 5 --warmup 2 --msg-mib 64 \
            --pp-iters 100 > "$OLDPWD/gpurun_out/rocprof.log" 2>&1 ) \
         && echo OK || echo "FAIL rc=$?"
 fi
