@@ -38,6 +38,8 @@ $(PYEXT): mpix/_core.o $(OBJS)
 %.o: %.cpp src/internal.h include/mpix/mpix.h include/mpix/mpix_abi.h
 	$(HIPCC) $(CXXFLAGS) -c $< -o $@
 
+src/transport/native.o: src/transport/pull_plan.h
+
 $(LIB): $(OBJS)
 	$(HIPCC) --offload-arch=$(GPU_ARCH) $(OBJS) $(LDFLAGS) -o $@
 

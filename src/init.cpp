@@ -625,6 +625,23 @@ extern "C" int MPIX_Finalize(void)
                     (double)s->leg_trig_ns / k, (double)s->leg_xfer_ns / k,
                     (double)s->leg_compl_ns / k);
         }
+        if (s->bleg_n) {
+            double k = 1e3 * (double)s->bleg_n;
+            fprintf(stderr,
+                    "[mpix stats r%d] pull-batch mean us over %lu batches "
+                    "(%.1f ops, %.1f copies each): first-pending->launch "
+                    "%.1f (launch call %.1f, event record %.1f), "
+                    "launch->event %.1f, "
+                    "event->last-completed %.1f\n",
+                    s->world_rank, (unsigned long)s->bleg_n,
+                    (double)s->bleg_items / (double)s->bleg_n,
+                    (double)s->bleg_copies / (double)s->bleg_n,
+                    (double)s->bleg_wait_ns / k,
+                    (double)s->bleg_call_ns / k, (double)s->bleg_rec_ns / k,
+                    (double)s->bleg_kernel_ns / k,
+                    s->bleg_done_n ? (double)s->bleg_done_ns / 1e3 /
+                                         (double)s->bleg_done_n : 0.0);
+        }
     }
 
     if (s->t_native) {

@@ -115,6 +115,14 @@ struct ChStatus {
 
 enum class OpKind : int32_t { NONE = 0, ISEND, IRECV, PSEND_PART, PRECV_PART };
 
+/* MPIX_STATS=1: shared by the receive ops of one batched pull, from the
+ * moment its event was seen complete until the last of them is COMPLETED
+ * (proxy thread only). */
+struct BatchStat {
+    uint64_t t_ev_ns; /* batch event seen complete */
+    int left;         /* ops of the batch not yet COMPLETED */
+};
+
 /* One in-flight operation, bound 1:1 to a flag slot. */
 struct Op {
     OpKind kind = OpKind::NONE;
@@ -139,6 +147,7 @@ struct Op {
     std::atomic<int> ch_done{0};
     ChStatus ch_status;
     void *ch_priv = nullptr;        /* channel-private per-op state */
+    BatchStat *stat_batch = nullptr; /* batched pull it rode (MPIX_STATS=1) */
 
     /* completion/status delivery (guarded by g_state->completion_mutex) */
     bool fast = false;              /* fast-wait protocol op */
@@ -159,7 +168,7 @@ struct Op {
         partition = -1; pseq = 0; req = nullptr;
         t_enq_ns = 0; t_issue_ns = 0;
         ch_done.store(0, std::memory_order_relaxed);
-        ch_status = ChStatus{}; ch_priv = nullptr;
+        ch_status = ChStatus{}; ch_priv = nullptr; stat_batch = nullptr;
         fast = false; waiter_owns_req = false;
         enq_status_target = nullptr; status_saved = false;
         orphaned.store(false, std::memory_order_relaxed);
@@ -327,6 +336,15 @@ struct State {
      * done->completion-published */
     uint64_t leg_trig_ns = 0, leg_xfer_ns = 0, leg_compl_ns = 0;
     uint64_t leg_n = 0;
+    /* batch-level legs of the batched pull (proxy thread only): both sides
+     * of the batch's first partition seen PENDING -> pull launch issued,
+     * launch issued -> batch event seen complete, event complete -> last op
+     * of the batch COMPLETED */
+    uint64_t bleg_wait_ns = 0, bleg_kernel_ns = 0, bleg_done_ns = 0;
+    /* parts of bleg_wait: the kernel launch call, the event record call */
+    uint64_t bleg_call_ns = 0, bleg_rec_ns = 0;
+    uint64_t bleg_n = 0, bleg_done_n = 0;
+    uint64_t bleg_items = 0, bleg_copies = 0; /* ops / merged copies */
 };
 
 extern State *g_state;

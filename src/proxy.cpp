@@ -65,7 +65,17 @@ static bool trace_on()
     return v != 0;
 }
 
-#define MPIX_TRACE_EV(fmt, ...)                                           \
+/* MPIX_STATS=1: `op` has just been published complete; the last op of a
+ * batched pull closes the batch's event -> COMPLETED leg. */
+static void batch_stat_op_done(State *s, BatchStat *bs)
+{
+    if (bs == nullptr || --bs->left > 0) return;
+    s->bleg_done_ns += now_ns() - bs->t_ev_ns;
+    s->bleg_done_n++;
+    delete bs;
+}
+
+#define MPIX_TRACE_EV(fmt, ...)                                         \
     do {                                                                  \
         if (trace_on())                                                   \
             fprintf(stderr, "[mpix trace r%d] " fmt "\n",                 \
@@ -191,6 +201,7 @@ void proxy_main()
                     MPIX_TRACE_EV("slot %d fast complete seq=%u err=%d", idx,
                                   req->seq, op->ch_status.err);
                     seq_store(idx, req->seq);
+                    batch_stat_op_done(s, op->stat_batch);
                     if (free_req) delete req;
                     s->ops_completed.fetch_add(1, std::memory_order_relaxed);
                     slot_free(idx);
@@ -213,13 +224,17 @@ void proxy_main()
                     MPIX_TRACE_EV("slot %d ISSUED->COMPLETED err=%d", idx,
                                   op->ch_status.err);
                     uint64_t tc = s->stats ? now_ns() : 0;
+                    BatchStat *bs = op->stat_batch; /* op may be recycled */
+                    op->stat_batch = nullptr;
                     if (complete_op(idx, op)) { /* orphan: slot freed */
                         if (s->stats) s->leg_compl_ns += now_ns() - tc;
+                        batch_stat_op_done(s, bs);
                         drop(i);
                         did = true;
                         continue;
                     }
                     if (s->stats) s->leg_compl_ns += now_ns() - tc;
+                    batch_stat_op_done(s, bs);
                     did = true;
                 }
                 break;

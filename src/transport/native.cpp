@@ -43,35 +43,87 @@
 
 #include "../internal.h"
 #include "bootstrap.h"
+#include "pull_plan.h"
 
 namespace mpix {
 
 /* Batched pull: one launch copies every partition/message that became
  * ready in the same progress pass (a 64 x 4 MiB partitioned step was
- * latency-bound at ~9 us per serialized launch+event).  All blocks stripe
- * over each copy in turn — balanced regardless of size mix.  Args live in
- * pinned mapped memory (an 8-slot ring reused after the batch's event). */
-#define MPIX_PULL_BATCH 64
-struct PullArg {
-    void *dst;
-    const void *src;
-    size_t n16;   /* 16-byte vectors */
-    size_t tail;  /* leftover bytes after n16*16 */
-};
+ * latency-bound at ~9 us per serialized launch+event).  The host plans the
+ * batch (pull_plan.h): contiguous entries merge into one copy and every copy
+ * is cut into tiles of 256 threads x U x 16 B.  Blocks grid-stride over the
+ * TOTAL tile count, so they finish together whatever the size mix.  The
+ * table travels by value in the kernel argument: no block reads host memory,
+ * and there is no argument ring to recycle.  Per full tile a thread issues
+ * its U 16-byte loads into independent registers before the first store
+ * (U x 4 KiB in flight per block), through global-address-space pointers so
+ * the accesses are global_*, not flat_*, and nontemporal by default: the
+ * payload is touched once, and keeping it out of the caches is what
+ * measured faster than the one-vector-per-thread kernel this replaces
+ * (profiles/pull_stream_copy.md).  The partial last tile of a copy
+ * and its n % 16 tail bytes take the slow branch.  No spin-wait and no
+ * completion signal in here: completion stays the event recorded behind
+ * the launch (see maybe_switch_prio for why nothing may park on a queue). */
+#define PULL_THREADS 256
+typedef unsigned int pull_v4 __attribute__((ext_vector_type(4)));
+typedef const __attribute__((address_space(1))) pull_v4 *pull_gsrc;
+typedef __attribute__((address_space(1))) pull_v4 *pull_gdst;
 
-__global__ void k_pull_multi(const PullArg *__restrict__ args, int ncopies)
+template <bool NT>
+static __device__ __forceinline__ pull_v4 pull_ld(pull_gsrc p)
 {
-    size_t gid = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-    size_t stride = (size_t)gridDim.x * blockDim.x;
-    for (int c = 0; c < ncopies; c++) {
-        const uint4 *s4 = (const uint4 *)args[c].src;
-        uint4 *d4 = (uint4 *)args[c].dst;
-        size_t nv = args[c].n16;
-        for (size_t v = gid; v < nv; v += stride) d4[v] = s4[v];
-        if (gid == 0)
-            for (size_t b = 0; b < args[c].tail; b++)
-                ((char *)args[c].dst)[nv * 16 + b] =
-                    ((const char *)args[c].src)[nv * 16 + b];
+    return NT ? __builtin_nontemporal_load(p) : *p;
+}
+
+template <bool NT>
+static __device__ __forceinline__ void pull_st(pull_gdst p, pull_v4 v)
+{
+    if (NT)
+        __builtin_nontemporal_store(v, p);
+    else
+        *p = v;
+}
+
+template <int U, bool NT>
+__global__ __launch_bounds__(PULL_THREADS) void k_pull_multi(const PullTable t)
+{
+    constexpr uint64_t TILE = (uint64_t)PULL_THREADS * U * 16;
+    const uint64_t total = t.tile_end[t.ncopies - 1];
+    /* copy c holds global tiles [first, end); the table sits in the kernel
+     * argument and is re-read only when a block crosses into another copy */
+    uint32_t c = 0;
+    uint64_t first = 0, end = t.tile_end[0];
+    PullCopy cur = t.copy[0];
+    for (uint64_t tile = blockIdx.x; tile < total; tile += gridDim.x) {
+        if (tile >= end) {
+            do {
+                first = end;
+                end = t.tile_end[++c];
+            } while (tile >= end);
+            cur = t.copy[c];
+        }
+        const uint64_t off = (tile - first) * TILE;
+        const uint64_t left = cur.bytes - off;
+        pull_gsrc s = (pull_gsrc)(cur.src + off);
+        pull_gdst d = (pull_gdst)(cur.dst + off);
+        if (left >= TILE) {
+            pull_v4 r[U];
+#pragma unroll
+            for (int k = 0; k < U; k++)
+                r[k] = pull_ld<NT>(s + threadIdx.x + k * PULL_THREADS);
+#pragma unroll
+            for (int k = 0; k < U; k++)
+                pull_st<NT>(d + threadIdx.x + k * PULL_THREADS, r[k]);
+        } else {
+            const uint32_t nv = (uint32_t)(left / 16);
+            for (uint32_t v = threadIdx.x; v < nv; v += PULL_THREADS)
+                d[v] = s[v];
+            if (threadIdx.x < (uint32_t)(left & 15)) {
+                const uint64_t b = (uint64_t)nv * 16 + threadIdx.x;
+                ((__attribute__((address_space(1))) char *)d)[b] =
+                    ((const __attribute__((address_space(1))) char *)s)[b];
+            }
+        }
     }
 }
 
@@ -85,6 +137,13 @@ static bool env_flag(const char *name)
 {
     const char *e = getenv(name);
     return e && atoi(e);
+}
+
+/* MPIX_TRACE=1, read once (as in proxy.cpp) */
+static bool trace_on()
+{
+    static const bool v = env_flag("MPIX_TRACE");
+    return v;
 }
 
 static uint64_t dev_push_max()
@@ -128,7 +187,10 @@ struct alignas(64) Desc {
     uint8_t ipc[64] = {};     /* DEV_NOTIFY: hipIpcMemHandle_t (or raw ptr) */
     uint64_t ipc_off = 0;
     int32_t src_dev = -1;
-    uint32_t _pad[9] = {};
+    uint32_t _pad0 = 0;
+    uint64_t t_seen_ns = 0;   /* DEV_NOTIFY: sender saw PENDING (MPIX_STATS=1;
+                                 steady clock, comparable across the node) */
+    uint32_t _pad[6] = {};
 };
 static_assert(sizeof(Desc) == 192, "Desc layout");
 
@@ -237,21 +299,17 @@ private:
         void *dst;
         const void *csrc;
         uint64_t n;
+        uint64_t t_seen_ns; /* both sides seen PENDING (MPIX_STATS=1) */
     };
     std::vector<PendingPull> pend_pulls_;
     struct PullBatch {
         hipEvent_t ev;
-        int slot;
+        uint64_t t_launch_ns; /* MPIX_STATS=1 */
         std::vector<PendingPull> items;
     };
     std::list<PullBatch> batches_;
-    /* pinned arg ring; per-slot busy flags because batches on different
-     * streams (MPIX_COPY_PRIO_STREAM=1) can complete out of order */
-    static constexpr int ARG_SLOTS = 8;
-    PullArg *args_h_ = nullptr;   /* pinned, ARG_SLOTS * MPIX_PULL_BATCH */
-    PullArg *args_d_ = nullptr;
-    int arg_slot_ = 0;
-    bool arg_busy_[ARG_SLOTS] = {};
+    PullTable plan_{}; /* scratch of flush_pulls; passed by value */
+    void launch_pull(unsigned blocks, hipStream_t cs);
 
     /* ---- shm ---- */
     ShmGeom geom_{};
@@ -485,15 +543,6 @@ int NativeTransport::init()
                 (void)hipGetLastError();
             }
         }
-        if (hipHostMalloc((void **)&args_h_,
-                          (size_t)ARG_SLOTS * MPIX_PULL_BATCH *
-                              sizeof(PullArg),
-                          hipHostMallocMapped) != hipSuccess ||
-            hipHostGetDevicePointer((void **)&args_d_, args_h_, 0) !=
-                hipSuccess) {
-            MPIX_ERR("pull-arg ring alloc failed");
-            return -1;
-        }
     }
     return 0;
 }
@@ -514,8 +563,6 @@ void NativeTransport::shutdown()
     }
     if (copy_plain0_) (void)hipStreamDestroy(copy_plain0_);
     copy_plain0_ = nullptr;
-    if (args_h_) (void)hipHostFree(args_h_);
-    args_h_ = nullptr;
     for (int r = 0; r < (int)seg_.size(); r++)
         if (seg_[r]) munmap(seg_[r], geom_.segment_bytes);
     seg_.clear();
@@ -545,6 +592,9 @@ void NativeTransport::put_event(hipEvent_t ev) { event_pool_.push_back(ev); }
 
 int NativeTransport::start(Op *op)
 {
+    /* the proxy stamps this again after start() returns; the batch legs
+     * need it already while the op is matched in here */
+    if (g_state->stats) op->t_issue_ns = now_ns();
     switch (op->kind) {
     case OpKind::ISEND:
     case OpKind::PSEND_PART:
@@ -633,6 +683,7 @@ int NativeTransport::progress_sends()
                 d.partition = op->partition;
                 d.msg_bytes = op->bytes;
                 d.src_dev = dev_;
+                d.t_seen_ns = op->t_issue_ns;
                 if (dst == rank_) {
                     d.flags |= DESCF_SELF_PTR;
                     uint64_t p = (uint64_t)(uintptr_t)op->buf;
@@ -903,8 +954,10 @@ void NativeTransport::start_dev_copy(InboundMsg &m)
     if (n > 0 && kernel_ok) {
         /* defer: every pull that matched in this progress pass goes out in
          * ONE k_pull_multi launch (flush_pulls) */
+        uint64_t seen = op->t_issue_ns > m.d.t_seen_ns ? op->t_issue_ns
+                                                       : m.d.t_seen_ns;
         pend_pulls_.push_back(PendingPull{op, m.src, m.d.token, st,
-                                          op->buf, src, n});
+                                          op->buf, src, n, seen});
         m.dev_copy_started = true;
         erase_inbound(&m);
         return;
@@ -923,7 +976,7 @@ void NativeTransport::start_dev_copy(InboundMsg &m)
         erase_inbound(&m);
         return;
     }
-    if (getenv("MPIX_TRACE") && atoi(getenv("MPIX_TRACE")))
+    if (trace_on())
         fprintf(stderr, "[mpix trace] pull start %lu B via memcpyAsync "
                 "(dst=%p src=%p)\n", (unsigned long)n, op->buf, src);
     hipEvent_t ev = get_event();
@@ -935,40 +988,86 @@ void NativeTransport::start_dev_copy(InboundMsg &m)
     erase_inbound(&m);
 }
 
+/* Kernel variant knobs, read once; the defaults are the measured winners
+ * (profiles/pull_stream_copy.md).  MPIX_PULL_UNROLL = 4 (default) or 8
+ * vectors per thread and tile, or 1, which is the access pattern of the
+ * earlier kernel.  MPIX_PULL_NT=0 turns the nontemporal loads and stores
+ * off: the payload is touched once and is far larger than L2, and keeping
+ * it out of the caches is where the gain over the earlier kernel comes
+ * from (with plain accesses the tiled kernel is slower than that one). */
+static int pull_unroll()
+{
+    static const int v = [] {
+        const char *e = getenv("MPIX_PULL_UNROLL");
+        int u = e ? atoi(e) : 4;
+        return u == 1 || u == 8 ? u : 4;
+    }();
+    return v;
+}
+
+static bool pull_nontemporal()
+{
+    static const bool v = [] {
+        const char *e = getenv("MPIX_PULL_NT");
+        return e ? atoi(e) != 0 : true;
+    }();
+    return v;
+}
+
+template <int U>
+static void launch_pull_u(bool nt, unsigned blocks, hipStream_t cs,
+                          const PullTable &t)
+{
+    if (nt)
+        hipLaunchKernelGGL((k_pull_multi<U, true>), dim3(blocks),
+                           dim3(PULL_THREADS), 0, cs, t);
+    else
+        hipLaunchKernelGGL((k_pull_multi<U, false>), dim3(blocks),
+                           dim3(PULL_THREADS), 0, cs, t);
+}
+
+void NativeTransport::launch_pull(unsigned blocks, hipStream_t cs)
+{
+    const bool nt = pull_nontemporal();
+    switch (pull_unroll()) {
+    case 1: launch_pull_u<1>(nt, blocks, cs, plan_); break;
+    case 8: launch_pull_u<8>(nt, blocks, cs, plan_); break;
+    default: launch_pull_u<4>(nt, blocks, cs, plan_); break;
+    }
+}
+
 void NativeTransport::flush_pulls()
 {
+    const bool stats = g_state != nullptr && g_state->stats;
+    const uint64_t tile_bytes = (uint64_t)PULL_THREADS * pull_unroll() * 16;
     while (!pend_pulls_.empty()) {
-        if (arg_busy_[arg_slot_]) return; /* ring full: next pass */
-        int n = (int)pend_pulls_.size();
+        PullSeg segs[MPIX_PULL_BATCH];
+        size_t n = pend_pulls_.size();
         if (n > MPIX_PULL_BATCH) n = MPIX_PULL_BATCH;
-        PullArg *slot_h = args_h_ + (size_t)arg_slot_ * MPIX_PULL_BATCH;
-        PullArg *slot_d = args_d_ + (size_t)arg_slot_ * MPIX_PULL_BATCH;
         uint64_t total = 0;
-        for (int i = 0; i < n; i++) {
+        uint64_t t_first = UINT64_MAX;
+        for (size_t i = 0; i < n; i++) {
             const PendingPull &pp = pend_pulls_[i];
-            slot_h[i].dst = pp.dst;
-            slot_h[i].src = pp.csrc;
-            slot_h[i].n16 = pp.n / 16;
-            slot_h[i].tail = pp.n % 16;
+            segs[i] = PullSeg{pp.dst, pp.csrc, pp.n};
             total += pp.n;
+            if (pp.t_seen_ns < t_first) t_first = pp.t_seen_ns;
         }
+        plan_pulls(segs, n, tile_bytes, &plan_);
         hipStream_t cs = copy_stream(total);
-        unsigned threads = 256;
         static const unsigned max_blocks = [] {
             const char *e = getenv("MPIX_PULL_BLOCKS");
-            /* A/B @256 MiB batches: 512 -> 1411 GB/s, 1024 -> 1700,
-             * 2048 -> 1594 (4 blocks/CU fills HBM without thrash) */
+            /* cap on blocks; A/B in profiles/pull_stream_copy.md */
             return e && atoi(e) > 0 ? (unsigned)atoi(e) : 1024u;
         }();
-        unsigned blocks = (unsigned)((total / 16 + threads - 1) / threads);
-        if (blocks == 0) blocks = 1;
-        if (blocks > max_blocks) blocks = max_blocks;
-        hipLaunchKernelGGL(k_pull_multi, dim3(blocks), dim3(threads), 0, cs,
-                           slot_d, n);
+        uint64_t tiles = pull_total_tiles(plan_);
+        unsigned blocks = tiles < max_blocks ? (unsigned)tiles : max_blocks;
+        const uint64_t t_call = stats ? now_ns() : 0;
+        launch_pull(blocks, cs);
         hipError_t e = hipGetLastError();
+        const uint64_t t_rec = stats ? now_ns() : 0;
         if (e != hipSuccess) {
             MPIX_ERR("k_pull_multi launch failed: %s", hipGetErrorString(e));
-            for (int i = 0; i < n; i++) {
+            for (size_t i = 0; i < n; i++) {
                 PendingPull &pp = pend_pulls_[i];
                 pp.st.err = MPI_ERR_OTHER;
                 pp.op->ch_status = pp.st;
@@ -980,16 +1079,24 @@ void NativeTransport::flush_pulls()
         }
         PullBatch b;
         b.ev = get_event();
-        b.slot = arg_slot_;
         (void)hipEventRecord(b.ev, cs);
+        b.t_launch_ns = 0;
+        if (stats) {
+            b.t_launch_ns = now_ns();
+            g_state->bleg_wait_ns += b.t_launch_ns - t_first;
+            g_state->bleg_call_ns += t_rec - t_call;
+            g_state->bleg_rec_ns += b.t_launch_ns - t_rec;
+            g_state->bleg_n++;
+            g_state->bleg_items += n;
+            g_state->bleg_copies += plan_.ncopies;
+        }
         b.items.assign(pend_pulls_.begin(), pend_pulls_.begin() + n);
         pend_pulls_.erase(pend_pulls_.begin(), pend_pulls_.begin() + n);
         batches_.push_back(std::move(b));
-        arg_busy_[arg_slot_] = true;
-        arg_slot_ = (arg_slot_ + 1) % ARG_SLOTS;
-        if (getenv("MPIX_TRACE") && atoi(getenv("MPIX_TRACE")))
-            fprintf(stderr, "[mpix trace] pull batch n=%d total=%lu B\n", n,
-                    (unsigned long)total);
+        if (trace_on())
+            fprintf(stderr, "[mpix trace] pull batch n=%zu copies=%u "
+                    "tiles=%lu total=%lu B\n", n, plan_.ncopies,
+                    (unsigned long)tiles, (unsigned long)total);
     }
 }
 
@@ -1002,8 +1109,14 @@ int NativeTransport::progress_copies()
             continue;
         }
         put_event(it->ev);
+        BatchStat *bs = nullptr;
+        if (it->t_launch_ns) {
+            bs = new BatchStat{now_ns(), (int)it->items.size()};
+            g_state->bleg_kernel_ns += bs->t_ev_ns - it->t_launch_ns;
+        }
         for (PendingPull &pp : it->items) {
             if (e != hipSuccess) pp.st.err = MPI_ERR_OTHER;
+            pp.op->stat_batch = bs;
             if (ring_has_space(pp.src, 1)) {
                 Desc d;
                 d.type = DESC_DONE;
@@ -1016,7 +1129,6 @@ int NativeTransport::progress_copies()
             pp.op->ch_status = pp.st;
             pp.op->ch_done.store(1, std::memory_order_release);
         }
-        arg_busy_[it->slot] = false;
         it = batches_.erase(it);
     }
     for (auto it = copies_.begin(); it != copies_.end();) {
@@ -1026,7 +1138,7 @@ int NativeTransport::progress_copies()
             continue;
         }
         if (e != hipSuccess) it->st.err = MPI_ERR_OTHER;
-        if (getenv("MPIX_TRACE") && atoi(getenv("MPIX_TRACE")))
+        if (trace_on())
             fprintf(stderr, "[mpix trace] pull done (e=%d)\n", (int)e);
         put_event(it->ev);
         /* ack the sender, then complete the recv */
