@@ -29,16 +29,19 @@ all: $(LIB) python
 python: $(PYEXT)
 
 mpix/_core.o: mpix/_core.cpp include/mpix/mpix.h include/mpix/mpix_device.h \
-              include/mpix/mpix_abi.h
+              include/mpix/mpix_abi.h include/mpix/mpix_layout.h
 	$(HIPCC) $(CXXFLAGS) -I$(PYINC) -I$(PYBIND11INC) -c mpix/_core.cpp -o $@
 
 $(PYEXT): mpix/_core.o $(OBJS)
 	$(HIPCC) --offload-arch=$(GPU_ARCH) mpix/_core.o $(OBJS) $(LDFLAGS) -o $@
 
-%.o: %.cpp src/internal.h include/mpix/mpix.h include/mpix/mpix_abi.h
+%.o: %.cpp src/internal.h include/mpix/mpix.h include/mpix/mpix_abi.h \
+     include/mpix/mpix_layout.h
 	$(HIPCC) $(CXXFLAGS) -c $< -o $@
 
-src/transport/native.o: src/transport/pull_plan.h
+src/transport/native.o: src/transport/pull_plan.h src/transport/layout.h \
+                        src/transport/strided_plan.h
+src/enqueue.o: src/transport/layout.h
 
 $(LIB): $(OBJS)
 	$(HIPCC) --offload-arch=$(GPU_ARCH) $(OBJS) $(LDFLAGS) -o $@

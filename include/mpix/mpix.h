@@ -29,6 +29,8 @@
 
 #include <mpi.h>
 
+#include "mpix_layout.h"
+
 #ifdef __cplusplus
 extern "C" {
 #endif
@@ -70,6 +72,30 @@ int MPIX_Isend_enqueue(const void *buf, int count, MPI_Datatype datatype,
 int MPIX_Irecv_enqueue(void *buf, int count, MPI_Datatype datatype,
                        int source, int tag, MPI_Comm comm, MPIX_Request *request,
                        int qtype, void *queue);
+
+/* Strided variants: `buf` is laid out as *layout (mpix_layout.h: a
+ * contiguous run plus up to two strided levels) and the message is its bytes
+ * in (plane, run, byte) order, layout->run_bytes * count[0] * count[1] of
+ * them.  As with MPI datatypes only that byte sequence has to agree between
+ * the two sides: either side may be strided, contiguous (the plain calls) or
+ * strided differently.  Device buffers are moved by one kernel that walks
+ * both layouts (no pack, no unpack, no staging); host buffers are staged run
+ * by run.  Requests behave exactly like those of the plain calls (stream and
+ * graph queues, captures, MPIX_Wait*_enqueue, status byte count, truncation).
+ * Errors: MPI_ERR_ARG for a layout with a stride that is zero, negative or
+ * smaller than what it steps over (overlap), or whose size overflows;
+ * MPI_ERR_TYPE at enqueue for a communicator served by the MPI passthrough
+ * transport, and as the completion status when one buffer is in device and
+ * the other in host memory (plain messages between the two kinds work).
+ * Not supported: partitioned requests with layouts, decoding
+ * MPI_Type_vector / subarray handles, more than two strided levels. */
+int MPIX_Isend_strided_enqueue(const void *buf, const MPIX_Layout *layout,
+                               int dest, int tag, MPI_Comm comm,
+                               MPIX_Request *request, int qtype, void *queue);
+
+int MPIX_Irecv_strided_enqueue(void *buf, const MPIX_Layout *layout,
+                               int source, int tag, MPI_Comm comm,
+                               MPIX_Request *request, int qtype, void *queue);
 
 int MPIX_Wait_enqueue(MPIX_Request *req, MPI_Status *status, int qtype,
                       void *queue);

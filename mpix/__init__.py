@@ -59,6 +59,87 @@ def _addr_len(buf, nbytes=None):
     return int(addr), int(n)
 
 
+def _layout_of(buf):
+    """Layout of a non-contiguous tensor / ndarray view, or None when `buf`
+    is contiguous (C order), a tuple, or empty.
+
+    Returns (address, (run_bytes, count0, count1, stride0, stride1)): the
+    view's elements in C order are runs of run_bytes bytes, count0 of them
+    stride0 bytes apart per plane, count1 planes stride1 bytes apart
+    (MPIX_Layout).  Dimensions are collapsed from the innermost outwards;
+    a view that needs more than a run plus two strided levels, or that has
+    zero or negative strides (expand, flip) or steps backwards over itself
+    (a transpose), raises ValueError."""
+    if hasattr(buf, "data_ptr"):  # torch tensor
+        if buf.is_contiguous() or buf.numel() == 0:
+            return None
+        item = buf.element_size()
+        shape = tuple(buf.shape)
+        strides = tuple(s * item for s in buf.stride())
+        addr = buf.data_ptr()
+    elif hasattr(buf, "ctypes"):  # numpy array
+        if buf.flags["C_CONTIGUOUS"] or buf.size == 0:
+            return None
+        item = buf.itemsize
+        shape = tuple(buf.shape)
+        strides = tuple(buf.strides)
+        addr = buf.ctypes.data
+    else:
+        return None
+
+    def bad(why):
+        return ValueError(
+            f"cannot send/receive a view of shape {shape} with byte strides "
+            f"{strides}: {why}")
+
+    run = item
+    levels = []  # [count, stride], innermost first
+    for size, stride in zip(reversed(shape), reversed(strides)):
+        if size == 1:
+            continue
+        if stride <= 0:
+            raise bad("zero or negative strides (expand, flip) are not "
+                      "supported")
+        if not levels and stride == run:
+            run *= size
+        elif levels and stride == levels[-1][0] * levels[-1][1]:
+            levels[-1][0] *= size
+        else:
+            levels.append([size, stride])
+    if len(levels) > 2:
+        raise bad("it does not collapse into a contiguous run plus two "
+                  "strided levels")
+    extent = run
+    for count, stride in levels:
+        if stride < extent:
+            raise bad("an outer dimension steps over less than the inner "
+                      "ones span (transposed or overlapping view)")
+        extent = stride * (count - 1) + extent
+    while len(levels) < 2:
+        levels.append([1, extent])
+    return int(addr), (int(run), int(levels[0][0]), int(levels[1][0]),
+                       int(levels[0][1]), int(levels[1][1]))
+
+
+def _sendrecv(is_send, buf, peer, tag, qtype, stream, nbytes):
+    """Contiguous buffers and (addr, nbytes) tuples take the plain bindings;
+    non-contiguous views go out as a layout."""
+    lay = _layout_of(buf)
+    if lay is None:
+        addr, n = _addr_len(buf, nbytes)
+        if qtype == QUEUE_GRAPH:
+            f = _C.isend_graph if is_send else _C.irecv_graph
+            return f(addr, n, peer, tag)
+        f = _C.isend_enqueue if is_send else _C.irecv_enqueue
+        return f(addr, n, peer, tag, QUEUE_STREAM, _stream_addr(stream))
+    if nbytes is not None:
+        raise ValueError("nbytes= cannot be combined with a non-contiguous "
+                         "buffer: the view defines the message")
+    addr, (run, c0, c1, s0, s1) = lay
+    return _C.sendrecv_strided(is_send, addr, run, c0, c1, s0, s1, peer, tag,
+                               qtype, _stream_addr(stream))
+
+
 def _stream_addr(stream):
     if stream is None:
         return 0
@@ -92,26 +173,23 @@ def config():
 
 
 def isend_enqueue(buf, dest, tag=0, stream=None, nbytes=None):
-    addr, n = _addr_len(buf, nbytes)
-    return _C.isend_enqueue(addr, n, dest, tag, QUEUE_STREAM,
-                            _stream_addr(stream))
+    """Send `buf`: a tensor / ndarray (contiguous or a strided view whose
+    elements go out in C order, see _layout_of) or an (address, nbytes)
+    pair."""
+    return _sendrecv(True, buf, dest, tag, QUEUE_STREAM, stream, nbytes)
 
 
 def irecv_enqueue(buf, source, tag=0, stream=None, nbytes=None):
-    addr, n = _addr_len(buf, nbytes)
-    return _C.irecv_enqueue(addr, n, source, tag, QUEUE_STREAM,
-                            _stream_addr(stream))
+    return _sendrecv(False, buf, source, tag, QUEUE_STREAM, stream, nbytes)
 
 
 def isend_graph(buf, dest, tag=0, nbytes=None):
     """Graph-construction enqueue: returns (request, graph_handle)."""
-    addr, n = _addr_len(buf, nbytes)
-    return _C.isend_graph(addr, n, dest, tag)
+    return _sendrecv(True, buf, dest, tag, QUEUE_GRAPH, None, nbytes)
 
 
 def irecv_graph(buf, source, tag=0, nbytes=None):
-    addr, n = _addr_len(buf, nbytes)
-    return _C.irecv_graph(addr, n, source, tag)
+    return _sendrecv(False, buf, source, tag, QUEUE_GRAPH, None, nbytes)
 
 
 def waitall_graph(reqs):

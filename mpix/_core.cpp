@@ -179,6 +179,43 @@ PYBIND11_MODULE(_C, m)
             py::cast(r, py::return_value_policy::take_ownership),
             (uintptr_t)g);
     });
+    /* strided variants: the layout comes as (run_bytes, count0, count1,
+     * stride0, stride1), derived from shape/strides in mpix/__init__.py;
+     * qtype GRAPH returns (request, graph), STREAM the request */
+    m.def("sendrecv_strided",
+          [](bool is_send, uintptr_t buf, uint64_t run_bytes, uint64_t count0,
+             uint64_t count1, int64_t stride0, int64_t stride1, int peer,
+             int tag, int qtype, uintptr_t stream) -> py::object {
+              MPIX_Layout l;
+              l.run_bytes = run_bytes;
+              l.count[0] = count0;
+              l.count[1] = count1;
+              l.stride[0] = stride0;
+              l.stride[1] = stride1;
+              auto *r = new MxRequest();
+              hipGraph_t g = nullptr;
+              void *q = qtype == MPIX_QUEUE_HIP_GRAPH ? (void *)&g
+                                                      : (void *)&stream;
+              int rc = is_send
+                  ? MPIX_Isend_strided_enqueue((const void *)buf, &l, peer, tag,
+                                               MPI_COMM_WORLD, &r->req, qtype,
+                                               q)
+                  : MPIX_Irecv_strided_enqueue((void *)buf, &l, peer, tag,
+                                               MPI_COMM_WORLD, &r->req, qtype,
+                                               q);
+              if (rc != 0) {
+                  delete r;
+                  throw std::runtime_error(
+                      "MPIX_I" + std::string(is_send ? "send" : "recv") +
+                      "_strided_enqueue failed, rc=" + std::to_string(rc));
+              }
+              py::object pr =
+                  py::cast(r, py::return_value_policy::take_ownership);
+              if (qtype == MPIX_QUEUE_HIP_GRAPH)
+                  return py::make_tuple(pr, (uintptr_t)g);
+              return pr;
+          });
+
     m.def("wait_graph", [](MxRequest *r) {
         /* per-request wait graph (the reference's composition style in
          * test/src/ring-all-graph-construction.c uses one per request) */

@@ -18,6 +18,7 @@
 #include <hip/hip_runtime.h>
 
 #include "internal.h"
+#include "transport/layout.h"
 
 namespace mpix {
 
@@ -276,11 +277,12 @@ static int fire_trigger(int idx, int qtype, void *queue, Request *req)
     return MPI_SUCCESS;
 }
 
-/* Common body of Isend/Irecv_enqueue. */
+/* Common body of Isend/Irecv_enqueue and their strided variants (`layout`
+ * non-null: count and datatype are ignored, the message is the layout's). */
 static int enqueue_sendrecv(bool is_send, void *buf, int count,
                             MPI_Datatype datatype, int peer, int tag,
                             MPI_Comm comm, MPIX_Request *request, int qtype,
-                            void *queue)
+                            void *queue, const MPIX_Layout *layout = nullptr)
 {
     State *s = g_state;
     if (s == nullptr) {
@@ -292,11 +294,34 @@ static int enqueue_sendrecv(bool is_send, void *buf, int count,
         return MPI_ERR_ARG;
 
     int tsz = 0;
-    MPIX_CHECK(datatype_size(datatype, &tsz));
+    MPIX_Layout norm = {};
+    if (layout != nullptr) {
+        if (layout_validate(*layout) != 0) {
+            MPIX_ERR("invalid layout: run %lu, counts %lu %lu, strides %ld "
+                     "%ld (strides must be positive and step over what lies "
+                     "below them; sizes must not overflow)",
+                     (unsigned long)layout->run_bytes,
+                     (unsigned long)layout->count[0],
+                     (unsigned long)layout->count[1], (long)layout->stride[0],
+                     (long)layout->stride[1]);
+            return MPI_ERR_ARG;
+        }
+        norm = layout_normalize(*layout);
+        datatype = MPI_BYTE;
+        uint64_t nb = layout_bytes(norm);
+        count = nb > (uint64_t)INT32_MAX ? INT32_MAX : (int)nb;
+    } else {
+        MPIX_CHECK(datatype_size(datatype, &tsz));
+    }
     int peer_world = -1;
     uint32_t comm_id = 0;
     bool native_ok = false;
     MPIX_CHECK(resolve_peer(comm, peer, &peer_world, &comm_id, &native_ok));
+    if (layout != nullptr && !native_ok) {
+        MPIX_ERR("strided transfers are served by the native transport only; "
+                 "this communicator resolves to the MPI passthrough");
+        return MPI_ERR_TYPE;
+    }
 
     int idx = slot_allocate();
     if (idx < 0) return MPI_ERR_INTERN;
@@ -307,6 +332,12 @@ static int enqueue_sendrecv(bool is_send, void *buf, int count,
     op->count = count;
     op->datatype = datatype;
     op->bytes = (uint64_t)count * (uint64_t)tsz;
+    if (layout != nullptr) {
+        /* a layout that is really contiguous takes the plain path unchanged */
+        op->bytes = layout_bytes(norm);
+        op->strided = !layout_is_contiguous(norm);
+        op->layout = norm;
+    }
     op->peer = peer;
     op->peer_world = peer_world;
     op->tag = tag;
@@ -364,6 +395,27 @@ extern "C" int MPIX_Irecv_enqueue(void *buf, int count, MPI_Datatype datatype,
 {
     return enqueue_sendrecv(false, buf, count, datatype, source, tag, comm,
                             request, qtype, queue);
+}
+
+extern "C" int MPIX_Isend_strided_enqueue(const void *buf,
+                                          const MPIX_Layout *layout, int dest,
+                                          int tag, MPI_Comm comm,
+                                          MPIX_Request *request, int qtype,
+                                          void *queue)
+{
+    if (layout == nullptr) return MPI_ERR_ARG;
+    return enqueue_sendrecv(true, (void *)buf, 0, MPI_BYTE, dest, tag, comm,
+                            request, qtype, queue, layout);
+}
+
+extern "C" int MPIX_Irecv_strided_enqueue(void *buf, const MPIX_Layout *layout,
+                                          int source, int tag, MPI_Comm comm,
+                                          MPIX_Request *request, int qtype,
+                                          void *queue)
+{
+    if (layout == nullptr) return MPI_ERR_ARG;
+    return enqueue_sendrecv(false, buf, 0, MPI_BYTE, source, tag, comm,
+                            request, qtype, queue, layout);
 }
 
 /* ----------------------------------------------------------- wait (stream) */

@@ -138,6 +138,10 @@ struct Op {
     bool buf_is_device = false;
     bool native_route = true;       /* native shm/xGMI channel vs MPI passthrough */
     int partition = -1;             /* >=0 for partitioned partial ops */
+    /* strided enqueue (MPIX_I*_strided_enqueue): buf is laid out as `layout`
+     * (normalised, not contiguous) and `bytes` is the message length */
+    bool strided = false;
+    MPIX_Layout layout = {};
     uint32_t pseq = 0;              /* partitioned iteration number */
     Request *req = nullptr;         /* owning request */
 
@@ -165,6 +169,7 @@ struct Op {
         datatype = MPI_DATATYPE_NULL; peer = peer_world = -1; tag = 0;
         comm = MPI_COMM_NULL; comm_id = 0; buf_is_device = false;
         native_route = true;
+        strided = false; layout = MPIX_Layout{};
         partition = -1; pseq = 0; req = nullptr;
         t_enq_ns = 0; t_issue_ns = 0;
         ch_done.store(0, std::memory_order_relaxed);

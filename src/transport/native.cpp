@@ -43,7 +43,9 @@
 
 #include "../internal.h"
 #include "bootstrap.h"
+#include "layout.h"
 #include "pull_plan.h"
+#include "strided_plan.h"
 
 namespace mpix {
 
@@ -127,6 +129,81 @@ __global__ __launch_bounds__(PULL_THREADS) void k_pull_multi(const PullTable t)
     }
 }
 
+/* Strided pull: the same launch shape for messages that are strided on
+ * either side (strided_plan.h).  Work is indexed in message space in units
+ * of the entry's granule, so a strided source lands straight in a strided
+ * destination: no pack, no unpack, no staging buffer.  Consecutive lanes take
+ * consecutive units, so lanes inside one run coalesce; a wave access made of
+ * 128-byte segments streams at full rate, 64 lanes in 64 different rows do
+ * not (4-byte runs are served correctly, not fast).  Per side a unit index
+ * decomposes into (plane, run, offset) by two divisions whose reciprocals
+ * the host prepared (a multiply and a shift each).  Granule 16 is the
+ * vector path: one global_load_dwordx4 / global_store_dwordx4 per unit,
+ * nontemporal, the U loads of a tile issued before its first store.  The
+ * element path is the same walk with 8/4/2/1-byte accesses, 16/granule
+ * rounds of it per tile.  Every unit is bounds-checked against the entry
+ * (the partial last tile takes the same code).  WIDE is the variant with
+ * 64-bit division, launched only when an entry has 2^31 units or more: it
+ * is many times the code, so the common kernel does not carry it. */
+template <typename T, int ROUNDS, bool WIDE>
+static __device__ __forceinline__ void strided_tile(const StridedEntry &e,
+                                                    uint64_t unit0)
+{
+    typedef const __attribute__((address_space(1))) T *gsrc;
+    typedef __attribute__((address_space(1))) T *gdst;
+    constexpr int U = MPIX_STRIDED_UNROLL;
+    constexpr bool wide = WIDE;
+#pragma unroll 1
+    for (int j = 0; j < ROUNDS; j++) {
+        T r[U];
+        int64_t doff[U];
+        bool ok[U];
+#pragma unroll
+        for (int k = 0; k < U; k++) {
+            const uint64_t u = unit0 +
+                (uint64_t)(j * U + k) * PULL_THREADS + threadIdx.x;
+            ok[k] = u < e.units;
+            if (ok[k]) {
+                r[k] = __builtin_nontemporal_load(
+                    (gsrc)(e.src + strided_side_offset(e.s, u, e.glog, wide)));
+                doff[k] = strided_side_offset(e.d, u, e.glog, wide);
+            }
+        }
+#pragma unroll
+        for (int k = 0; k < U; k++)
+            if (ok[k])
+                __builtin_nontemporal_store(r[k], (gdst)(e.dst + doff[k]));
+    }
+}
+
+template <bool WIDE>
+__global__ __launch_bounds__(PULL_THREADS) void k_pull_strided(
+    const StridedTable t)
+{
+    const uint64_t total = t.tile_end[t.n - 1];
+    uint32_t c = 0;
+    uint64_t first = 0, end = t.tile_end[0];
+    StridedEntry cur = t.e[0];
+    for (uint64_t tile = blockIdx.x; tile < total; tile += gridDim.x) {
+        if (tile >= end) {
+            do {
+                first = end;
+                end = t.tile_end[++c];
+            } while (tile >= end);
+            cur = t.e[c];
+        }
+        /* units of this tile start at (tile bytes) >> glog */
+        const uint64_t unit0 = ((tile - first) * MPIX_STRIDED_TILE) >> cur.glog;
+        switch (cur.glog) {
+        case 4: strided_tile<pull_v4, 1, WIDE>(cur, unit0); break;
+        case 3: strided_tile<uint64_t, 2, WIDE>(cur, unit0); break;
+        case 2: strided_tile<uint32_t, 4, WIDE>(cur, unit0); break;
+        case 1: strided_tile<uint16_t, 8, WIDE>(cur, unit0); break;
+        default: strided_tile<uint8_t, 16, WIDE>(cur, unit0); break;
+        }
+    }
+}
+
 /* Sender-push threshold for small DEVICE payloads: stage D2H into the shm
  * chunk ring like a host message (receiver H2D's it out), skipping the
  * NOTIFY/pull/ACK round trip.  Measured WORSE (74-97 us vs ~38 us half-RTT:
@@ -170,6 +247,7 @@ enum DescType : uint32_t {
 enum DescFlags : uint32_t {
     DESCF_PARTITIONED = 1u << 0,
     DESCF_SELF_PTR    = 1u << 1, /* ipc field holds a raw pointer (same proc) */
+    DESCF_STRIDED     = 1u << 2, /* layout field holds the sender's layout */
 };
 
 struct alignas(64) Desc {
@@ -190,9 +268,11 @@ struct alignas(64) Desc {
     uint32_t _pad0 = 0;
     uint64_t t_seen_ns = 0;   /* DEV_NOTIFY: sender saw PENDING (MPIX_STATS=1;
                                  steady clock, comparable across the node) */
-    uint32_t _pad[6] = {};
+    MPIX_Layout layout = {};  /* DEV_NOTIFY / first HOST_CHUNK of a message
+                                 with DESCF_STRIDED: the sender's normalised
+                                 layout (both ends are the same build) */
 };
-static_assert(sizeof(Desc) == 192, "Desc layout");
+static_assert(sizeof(Desc) == 192, "Desc layout"); /* layout took the pad */
 
 struct alignas(64) InboxHdr {
     alignas(64) std::atomic<uint64_t> head;       /* producer (peer proxy) */
@@ -276,6 +356,7 @@ private:
         std::vector<char> heap; /* unexpected host payload buffer */
         uint64_t got = 0;       /* host bytes received so far */
         bool dev_copy_started = false;
+        bool kind_mismatch = false; /* strided msg between host and device */
     };
     std::list<InboundMsg> inbound_;                 /* arrival order */
     std::unordered_map<uint64_t, InboundMsg *> inbound_by_token_;
@@ -310,6 +391,17 @@ private:
     std::list<PullBatch> batches_;
     PullTable plan_{}; /* scratch of flush_pulls; passed by value */
     void launch_pull(unsigned blocks, hipStream_t cs);
+
+    /* strided pulls collected this progress pass: ONE k_pull_strided launch
+     * per MPIX_STRIDED_BATCH of them, completed through batches_ like the
+     * contiguous ones */
+    struct PendingStrided {
+        PendingPull pp;
+        MPIX_Layout sl, dl; /* normalised source / destination layouts */
+    };
+    std::vector<PendingStrided> pend_strided_;
+    StridedTable splan_{}; /* scratch of flush_strided; passed by value */
+    bool strided_div64_ = false; /* MPIX_STRIDED_DIV64=1: see plan_strided */
 
     /* ---- shm ---- */
     ShmGeom geom_{};
@@ -434,6 +526,8 @@ private:
     int drain_inbox(int src);
     int progress_copies();
     void flush_pulls();
+    void flush_strided();
+    void fail_kind_mismatch(InboundMsg &m);
     void handle_desc(int src, const Desc &d, const char *stage_base);
     void try_match_new_inbound(InboundMsg &m);
     void attach(InboundMsg &m, Op *op);
@@ -515,6 +609,8 @@ int NativeTransport::init()
     out_head_.assign(size_, 0);
     out_stage_head_.assign(size_, 0);
     in_tail_.assign(size_, 0);
+
+    strided_div64_ = env_flag("MPIX_STRIDED_DIV64");
 
     if (have_gpu_) {
         if (hipStreamCreateWithFlags(&copy_streams_[0],
@@ -636,6 +732,7 @@ void NativeTransport::progress()
     progress_sends();
     for (int s = 0; s < size_; s++) drain_inbox(s);
     flush_pulls();
+    flush_strided();
     progress_copies();
 
     /* retry queued DONE acks */
@@ -671,7 +768,9 @@ int NativeTransport::progress_sends()
         while (!q.empty()) {
             SendState &ss = q.front();
             Op *op = ss.op;
-            if (op->buf_is_device && op->bytes > dev_push_max()) {
+            /* strided device sends always take the notify/pull path */
+            if (op->buf_is_device &&
+                (op->strided || op->bytes > dev_push_max())) {
                 if (!ring_has_space(dst, 1)) break;
                 Desc d;
                 d.type = DESC_DEV_NOTIFY;
@@ -684,6 +783,10 @@ int NativeTransport::progress_sends()
                 d.msg_bytes = op->bytes;
                 d.src_dev = dev_;
                 d.t_seen_ns = op->t_issue_ns;
+                if (op->strided) {
+                    d.flags |= DESCF_STRIDED;
+                    d.layout = op->layout;
+                }
                 if (dst == rank_) {
                     d.flags |= DESCF_SELF_PTR;
                     uint64_t p = (uint64_t)(uintptr_t)op->buf;
@@ -730,7 +833,10 @@ int NativeTransport::progress_sends()
                 if (n > 0) {
                     char *stage_dst = v.stage + chunk_idx * CHUNK_BYTES;
                     const char *payload = (const char *)op->buf + ss.staged;
-                    if (op->buf_is_device)
+                    if (op->strided) /* host buffer: device ones notify */
+                        layout_copy_out(stage_dst, op->buf, op->layout,
+                                        ss.staged, n);
+                    else if (op->buf_is_device)
                         memcpy_auto(stage_dst, payload, n); /* D2H */
                     else
                         memcpy(stage_dst, payload, n);
@@ -746,6 +852,10 @@ int NativeTransport::progress_sends()
                 d.msg_bytes = op->bytes;
                 d.chunk_off = ss.staged;
                 d.chunk_bytes = n;
+                if (op->strided && ss.staged == 0) {
+                    d.flags |= DESCF_STRIDED;
+                    d.layout = op->layout;
+                }
                 d.stage_chunk = chunk_idx;
                 out_stage_head_[dst]++;
                 emit_desc(dst, d);
@@ -852,11 +962,17 @@ void NativeTransport::attach(InboundMsg &m, Op *op)
         start_dev_copy(m);
         return;
     }
-    /* host message: move already-buffered bytes into the user buffer */
-    if (m.got > 0 && !m.heap.empty()) {
+    if ((op->strided || (m.d.flags & DESCF_STRIDED)) && op->buf_is_device) {
+        fail_kind_mismatch(m);
+    } else if (m.got > 0 && !m.heap.empty()) {
+        /* host message: move already-buffered bytes (message order) into
+         * the user buffer */
         uint64_t n = m.got;
         if (n > op->bytes) n = op->bytes;
-        if (n > 0) memcpy_auto(op->buf, m.heap.data(), n);
+        if (n > 0 && op->strided)
+            layout_copy_in(op->buf, op->layout, 0, m.heap.data(), n);
+        else if (n > 0)
+            memcpy_auto(op->buf, m.heap.data(), n);
     }
     m.heap.clear();
     m.heap.shrink_to_fit();
@@ -870,7 +986,13 @@ void NativeTransport::deliver_chunk(InboundMsg &m, const Desc &d,
         uint64_t room = (m.op->bytes > d.chunk_off)
                             ? m.op->bytes - d.chunk_off : 0;
         uint64_t n = d.chunk_bytes < room ? d.chunk_bytes : room;
-        if (n > 0)
+        /* kind_mismatch: payload dropped, the receive completes with
+         * MPI_ERR_TYPE */
+        if (m.kind_mismatch)
+            n = 0;
+        if (n > 0 && m.op->strided)
+            layout_copy_in(m.op->buf, m.op->layout, d.chunk_off, src_chunk, n);
+        else if (n > 0)
             memcpy_auto((char *)m.op->buf + d.chunk_off, src_chunk, n);
     } else {
         if (m.heap.size() < d.chunk_off + d.chunk_bytes)
@@ -892,8 +1014,26 @@ void NativeTransport::finish_host_recv(InboundMsg &m)
         m.d.msg_bytes <= op->bytes ? m.d.msg_bytes : op->bytes;
     op->ch_status.err =
         m.d.msg_bytes > op->bytes ? MPI_ERR_TRUNCATE : MPI_SUCCESS;
+    if (m.kind_mismatch) {
+        op->ch_status.bytes = 0;
+        op->ch_status.err = MPI_ERR_TYPE;
+    }
     op->ch_done.store(1, std::memory_order_release);
     erase_inbound(&m);
+}
+
+/* A strided message is served device-to-device (k_pull_strided) or
+ * host-to-host (layout_copy_out/in).  Between the two kinds it would take a
+ * synchronous copy per run or a kernel dereferencing pageable host memory;
+ * instead the receive completes with MPI_ERR_TYPE (and the sender completes:
+ * host sends are buffered, device sends are acked by the caller). */
+void NativeTransport::fail_kind_mismatch(InboundMsg &m)
+{
+    if (!m.kind_mismatch)
+        MPIX_ERR("strided transfers need both buffers in the same kind of "
+                 "memory (device or host): message from rank %d, tag %d "
+                 "fails with MPI_ERR_TYPE", m.src, m.d.tag);
+    m.kind_mismatch = true;
 }
 
 void *NativeTransport::map_remote(const Desc &d)
@@ -941,6 +1081,34 @@ void NativeTransport::start_dev_copy(InboundMsg &m)
     }
     uint64_t n = st.bytes;
     hipError_t e = hipSuccess;
+    const bool strided = op->strided || (m.d.flags & DESCF_STRIDED) != 0;
+    if (strided && !op->buf_is_device) {
+        fail_kind_mismatch(m);
+        st.bytes = 0;
+        st.err = MPI_ERR_TYPE;
+        op->ch_status = st;
+        op->ch_done.store(1, std::memory_order_release);
+        pending_done_.emplace_back(m.src, m.d.token);
+        erase_inbound(&m);
+        return;
+    }
+    if (strided && n > 0) {
+        /* defer: every strided pull that matched in this progress pass goes
+         * out in ONE k_pull_strided launch (flush_strided).  n is a multiple
+         * of the granule: it is the length of one of the two layouts, and the
+         * granule divides the runs of both. */
+        uint64_t seen = op->t_issue_ns > m.d.t_seen_ns ? op->t_issue_ns
+                                                       : m.d.t_seen_ns;
+        PendingStrided ps;
+        ps.pp = PendingPull{op, m.src, m.d.token, st, op->buf, src, n, seen};
+        ps.sl = (m.d.flags & DESCF_STRIDED) ? m.d.layout
+                                            : layout_contiguous(m.d.msg_bytes);
+        ps.dl = op->strided ? op->layout : layout_contiguous(op->bytes);
+        pend_strided_.push_back(ps);
+        m.dev_copy_started = true;
+        erase_inbound(&m);
+        return;
+    }
     /* The shader pull path requires (a) a device destination — dereferencing
      * a pageable host pointer from a kernel faults on non-XNACK systems —
      * and (b) 16-byte alignment on both sides (user buffers can be
@@ -1097,6 +1265,58 @@ void NativeTransport::flush_pulls()
             fprintf(stderr, "[mpix trace] pull batch n=%zu copies=%u "
                     "tiles=%lu total=%lu B\n", n, plan_.ncopies,
                     (unsigned long)tiles, (unsigned long)total);
+    }
+}
+
+void NativeTransport::flush_strided()
+{
+    while (!pend_strided_.empty()) {
+        StridedSeg segs[MPIX_STRIDED_BATCH];
+        size_t n = pend_strided_.size();
+        if (n > MPIX_STRIDED_BATCH) n = MPIX_STRIDED_BATCH;
+        uint64_t total = 0;
+        for (size_t i = 0; i < n; i++) {
+            const PendingStrided &ps = pend_strided_[i];
+            segs[i] = StridedSeg{ps.pp.dst, ps.pp.csrc, ps.pp.n, ps.sl, ps.dl};
+            total += ps.pp.n;
+        }
+        plan_strided(segs, n, strided_div64_, &splan_);
+        /* same stream choice as flush_pulls: a contiguous batch of this
+         * pass and this launch go back to back on the copy stream */
+        hipStream_t cs = copy_stream(total);
+        uint64_t tiles = strided_total_tiles(splan_);
+        unsigned blocks = tiles < 1024 ? (unsigned)tiles : 1024u;
+        if (strided_plan_wide(splan_))
+            hipLaunchKernelGGL(k_pull_strided<true>, dim3(blocks),
+                               dim3(PULL_THREADS), 0, cs, splan_);
+        else
+            hipLaunchKernelGGL(k_pull_strided<false>, dim3(blocks),
+                               dim3(PULL_THREADS), 0, cs, splan_);
+        hipError_t e = hipGetLastError();
+        if (e != hipSuccess) {
+            MPIX_ERR("k_pull_strided launch failed: %s", hipGetErrorString(e));
+            for (size_t i = 0; i < n; i++) {
+                PendingPull &pp = pend_strided_[i].pp;
+                pp.st.err = MPI_ERR_OTHER;
+                pp.op->ch_status = pp.st;
+                pp.op->ch_done.store(1, std::memory_order_release);
+                pending_done_.emplace_back(pp.src, pp.token);
+            }
+            pend_strided_.erase(pend_strided_.begin(),
+                                pend_strided_.begin() + n);
+            continue;
+        }
+        PullBatch b;
+        b.ev = get_event();
+        (void)hipEventRecord(b.ev, cs);
+        b.t_launch_ns = 0; /* the batch legs of MPIX_STATS count plain pulls */
+        for (size_t i = 0; i < n; i++) b.items.push_back(pend_strided_[i].pp);
+        pend_strided_.erase(pend_strided_.begin(), pend_strided_.begin() + n);
+        batches_.push_back(std::move(b));
+        if (trace_on())
+            fprintf(stderr, "[mpix trace] strided pull batch n=%zu tiles=%lu "
+                    "total=%lu B\n", n, (unsigned long)tiles,
+                    (unsigned long)total);
     }
 }
 
