@@ -625,19 +625,45 @@ extern "C" int MPIX_Finalize(void)
                     (double)s->leg_trig_ns / k, (double)s->leg_xfer_ns / k,
                     (double)s->leg_compl_ns / k);
         }
+        if (s->notify_descs)
+            fprintf(stderr,
+                    "[mpix stats r%d] device notifies: %lu descriptors for "
+                    "%lu messages sent, %lu messages received as part of a "
+                    "run on the fast path\n", s->world_rank,
+                    (unsigned long)s->notify_descs,
+                    (unsigned long)s->notify_msgs,
+                    (unsigned long)s->run_fast_msgs);
+        if (s->bleg_first_seen) {
+            /* on its own line and in none of the means below: this launch
+             * loads the code object */
+            fprintf(stderr,
+                    "[mpix stats r%d] pull-batch FIRST of the process, us "
+                    "(%lu ops): first-pending->launch %.1f (launch call "
+                    "%.1f, event record %.1f), launch->event %.1f, "
+                    "event->last-completed %.1f\n",
+                    s->world_rank, (unsigned long)s->bleg_first_items,
+                    (double)s->bleg_first_wait_ns / 1e3,
+                    (double)s->bleg_first_call_ns / 1e3,
+                    (double)s->bleg_first_rec_ns / 1e3,
+                    (double)s->bleg_first_kernel_ns / 1e3,
+                    (double)s->bleg_first_done_ns / 1e3);
+        }
         if (s->bleg_n) {
             double k = 1e3 * (double)s->bleg_n;
             fprintf(stderr,
                     "[mpix stats r%d] pull-batch mean us over %lu batches "
-                    "(%.1f ops, %.1f copies each): first-pending->launch "
-                    "%.1f (launch call %.1f, event record %.1f), "
-                    "launch->event %.1f, "
+                    "after the first (%.1f ops, %.1f copies each): "
+                    "first-pending->launch %.1f (launch call %.1f, min %.1f, "
+                    "max %.1f; event record %.1f), launch->event %.1f, "
                     "event->last-completed %.1f\n",
                     s->world_rank, (unsigned long)s->bleg_n,
                     (double)s->bleg_items / (double)s->bleg_n,
                     (double)s->bleg_copies / (double)s->bleg_n,
                     (double)s->bleg_wait_ns / k,
-                    (double)s->bleg_call_ns / k, (double)s->bleg_rec_ns / k,
+                    (double)s->bleg_call_ns / k,
+                    (double)s->bleg_call_min_ns / 1e3,
+                    (double)s->bleg_call_max_ns / 1e3,
+                    (double)s->bleg_rec_ns / k,
                     (double)s->bleg_kernel_ns / k,
                     s->bleg_done_n ? (double)s->bleg_done_ns / 1e3 /
                                          (double)s->bleg_done_n : 0.0);

@@ -121,6 +121,7 @@ enum class OpKind : int32_t { NONE = 0, ISEND, IRECV, PSEND_PART, PRECV_PART };
 struct BatchStat {
     uint64_t t_ev_ns; /* batch event seen complete */
     int left;         /* ops of the batch not yet COMPLETED */
+    bool first;       /* the first batch of the process (see bleg_first_*) */
 };
 
 /* One in-flight operation, bound 1:1 to a flag slot. */
@@ -350,6 +351,20 @@ struct State {
     uint64_t bleg_call_ns = 0, bleg_rec_ns = 0;
     uint64_t bleg_n = 0, bleg_done_n = 0;
     uint64_t bleg_items = 0, bleg_copies = 0; /* ops / merged copies */
+    /* shortest and longest launch call among the batches of the means */
+    uint64_t bleg_call_min_ns = UINT64_MAX, bleg_call_max_ns = 0;
+    /* The first batch of the process is kept out of all of the above and
+     * reported on its own: its launch loads the transport's code object,
+     * and with a few dozen batches in a run that one call moves the means
+     * by several us. */
+    /* DEV_NOTIFY descriptors sent and the messages they announced (a run of
+     * k partitions is one descriptor, part_run.h); messages received on the
+     * fast path of a run.  Proxy thread only, counted always. */
+    uint64_t notify_descs = 0, notify_msgs = 0, run_fast_msgs = 0;
+    bool bleg_first_seen = false;
+    uint64_t bleg_first_wait_ns = 0, bleg_first_call_ns = 0;
+    uint64_t bleg_first_rec_ns = 0, bleg_first_kernel_ns = 0;
+    uint64_t bleg_first_done_ns = 0, bleg_first_items = 0;
 };
 
 extern State *g_state;

@@ -70,8 +70,12 @@ static bool trace_on()
 static void batch_stat_op_done(State *s, BatchStat *bs)
 {
     if (bs == nullptr || --bs->left > 0) return;
-    s->bleg_done_ns += now_ns() - bs->t_ev_ns;
-    s->bleg_done_n++;
+    if (bs->first) {
+        s->bleg_first_done_ns = now_ns() - bs->t_ev_ns;
+    } else {
+        s->bleg_done_ns += now_ns() - bs->t_ev_ns;
+        s->bleg_done_n++;
+    }
     delete bs;
 }
 

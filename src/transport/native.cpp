@@ -12,6 +12,9 @@
  *                 pulls with hipMemcpyAsync over xGMI (SDMA) on a private
  *                 stream and acks with a DONE descriptor.  Same-process /
  *                 same-rank transfers skip IPC and use the raw pointer.
+ *                 Consecutive partitions of one request go out as a RUN:
+ *                 one descriptor, one pull, one DONE per acked range
+ *                 (part_run.h); an ack to ourselves skips the ring.
  *  host data      sender stages through the shm chunk ring (64 KiB chunks,
  *                 credit-based flow control); the receiver copies chunks
  *                 straight into the posted buffer (or an unexpected-message
@@ -44,6 +47,7 @@
 #include "../internal.h"
 #include "bootstrap.h"
 #include "layout.h"
+#include "part_run.h"
 #include "pull_plan.h"
 #include "strided_plan.h"
 
@@ -232,6 +236,18 @@ static uint64_t dev_push_max()
     return v;
 }
 
+/* MPIX_PART_RUNS=0, read once: the sender announces every partition with a
+ * descriptor of its own (runs of length 1 only), as before part_run.h.
+ * An A/B inside one build, and the way tests drive both protocols. */
+static bool part_runs_on()
+{
+    static const bool v = [] {
+        const char *e = getenv("MPIX_PART_RUNS");
+        return e ? atoi(e) != 0 : true;
+    }();
+    return v;
+}
+
 /* ------------------------------------------------------------- shm layout */
 
 static constexpr uint32_t RING_SLOTS_DEFAULT = 1024;
@@ -240,8 +256,10 @@ static constexpr uint32_t STAGE_CHUNKS_DEFAULT = 64; /* 4 MiB per pair */
 
 enum DescType : uint32_t {
     DESC_HOST_CHUNK = 1, /* one staged chunk of a host-buffer message */
-    DESC_DEV_NOTIFY = 2, /* device-buffer message advertisement */
-    DESC_DONE       = 3, /* receiver ack for DESC_DEV_NOTIFY */
+    DESC_DEV_NOTIFY = 2, /* device-buffer message advertisement, or a run of
+                            partitions (count > 1) */
+    DESC_DONE       = 3, /* receiver ack for DESC_DEV_NOTIFY: all of it, or
+                            the range {partition, count} of a run */
 };
 
 enum DescFlags : uint32_t {
@@ -257,15 +275,19 @@ struct alignas(64) Desc {
     int32_t src_world = -1;
     int32_t tag = 0;
     uint32_t comm_id = 0;
-    int32_t partition = -1;
-    uint64_t msg_bytes = 0;
+    int32_t partition = -1;   /* a run (count > 1): its first partition */
+    uint64_t msg_bytes = 0;   /* a run: the size of ONE partition */
     uint64_t chunk_off = 0;   /* HOST_CHUNK: offset of this chunk in the msg */
     uint64_t chunk_bytes = 0;
     uint64_t stage_chunk = 0; /* HOST_CHUNK: chunk index in the stage ring */
     uint8_t ipc[64] = {};     /* DEV_NOTIFY: hipIpcMemHandle_t (or raw ptr) */
     uint64_t ipc_off = 0;
     int32_t src_dev = -1;
-    uint32_t _pad0 = 0;
+    uint32_t count = 0;       /* DEV_NOTIFY: partitions partition ..
+                                 partition+count-1 of one request, slices of
+                                 one buffer msg_bytes apart (part_run.h);
+                                 DONE: that many partitions from `partition`
+                                 on are finished.  0 reads as 1. */
     uint64_t t_seen_ns = 0;   /* DEV_NOTIFY: sender saw PENDING (MPIX_STATS=1;
                                  steady clock, comparable across the node) */
     MPIX_Layout layout = {};  /* DEV_NOTIFY / first HOST_CHUNK of a message
@@ -343,10 +365,22 @@ private:
     };
     /* per-destination FIFO queues (preserves non-overtaking) */
     std::map<int, std::deque<SendState>> sendq_;
-    /* device sends awaiting DONE: token -> op */
-    std::unordered_map<uint64_t, Op *> await_done_;
+    /* device sends awaiting DONE: token (slot of the first op) -> the op,
+     * or the run of partitions announced under that token */
+    struct AwaitDone {
+        Op *op;       /* first (or only) op */
+        Request *req; /* owner of a run (k > 1), else unused */
+        RunAwait run;
+    };
+    std::unordered_map<uint64_t, AwaitDone> await_done_;
     /* pending DONE descriptors we could not emit (ring full) */
-    std::deque<std::pair<int, uint64_t>> pending_done_;
+    struct PendingDone {
+        int dst;
+        uint64_t token;
+        int32_t first;
+        uint32_t count;
+    };
+    std::deque<PendingDone> pending_done_;
 
     /* ---- recv side ---- */
     struct InboundMsg {
@@ -367,25 +401,42 @@ private:
         hipEvent_t ev;
         int src;
         uint64_t token;
+        int32_t partition;
         ChStatus st;
     };
     std::list<CopyInflight> copies_;
 
     /* pulls collected this progress pass, flushed as ONE kernel launch */
     struct PendingPull {
-        Op *op;
+        Op *op;             /* first (or only) receive */
         int src;
         uint64_t token;
-        ChStatus st;
+        ChStatus st;        /* of each of its receives */
         void *dst;
         const void *csrc;
-        uint64_t n;
+        uint64_t n;         /* all k receives together */
         uint64_t t_seen_ns; /* both sides seen PENDING (MPIX_STATS=1) */
+        int32_t partition;  /* of the first receive (for the ack) */
+        uint32_t k;         /* receives it completes: 1, or the partitions
+                               partition .. partition+k-1 of op->req, taken
+                               as one copy (the fast path of a run) */
     };
+    /* receive j of a pull */
+    static Op *pull_op(const PendingPull &pp, uint32_t j) {
+        return j == 0 ? pp.op
+                      : &g_state->ops[pp.op->req->part_idx[pp.partition + j]];
+    }
+    static size_t pull_ops(const std::vector<PendingPull> &v, size_t n) {
+        size_t ops = 0;
+        for (size_t i = 0; i < n; i++) ops += v[i].k;
+        return ops;
+    }
+    void finish_pull(const PendingPull &pp, BatchStat *bs);
     std::vector<PendingPull> pend_pulls_;
     struct PullBatch {
         hipEvent_t ev;
         uint64_t t_launch_ns; /* MPIX_STATS=1 */
+        bool first;           /* MPIX_STATS=1: first batch of the process */
         std::vector<PendingPull> items;
     };
     std::list<PullBatch> batches_;
@@ -529,6 +580,9 @@ private:
     void flush_strided();
     void fail_kind_mismatch(InboundMsg &m);
     void handle_desc(int src, const Desc &d, const char *stage_base);
+    bool try_run_fast_path(int src, const Desc &d, uint32_t k);
+    void ack(int src, uint64_t token, int32_t first, uint32_t count);
+    void handle_done(uint64_t token, int32_t first, uint32_t count);
     void try_match_new_inbound(InboundMsg &m);
     void attach(InboundMsg &m, Op *op);
     void start_dev_copy(InboundMsg &m);
@@ -737,13 +791,15 @@ void NativeTransport::progress()
 
     /* retry queued DONE acks */
     for (size_t i = 0; i < pending_done_.size();) {
-        auto [dst, token] = pending_done_[i];
-        if (ring_has_space(dst, 1)) {
+        const PendingDone pd = pending_done_[i];
+        if (ring_has_space(pd.dst, 1)) {
             Desc d;
             d.type = DESC_DONE;
-            d.token = token;
+            d.token = pd.token;
             d.src_world = rank_;
-            emit_desc(dst, d);
+            d.partition = pd.first;
+            d.count = pd.count;
+            emit_desc(pd.dst, d);
             pending_done_.erase(pending_done_.begin() + i);
         } else {
             i++;
@@ -772,8 +828,22 @@ int NativeTransport::progress_sends()
             if (op->buf_is_device &&
                 (op->strided || op->bytes > dev_push_max())) {
                 if (!ring_has_space(dst, 1)) break;
+                /* the run of partitions at the head of the queue goes out
+                 * as ONE descriptor (part_run.h); anything else is a run
+                 * of 1, today's descriptor */
+                size_t k = 1;
+                if (op->kind == OpKind::PSEND_PART && !op->strided &&
+                    part_runs_on())
+                    k = part_run_length(q.size(), [&q](size_t i) {
+                        const Op *o = q[i].op;
+                        return RunSend{o->req, o->pseq, o->partition,
+                                       o->bytes,
+                                       o->kind == OpKind::PSEND_PART,
+                                       o->buf_is_device, o->strided};
+                    }, dev_push_max());
                 Desc d;
                 d.type = DESC_DEV_NOTIFY;
+                d.count = (uint32_t)k;
                 d.flags = (op->kind == OpKind::PSEND_PART) ? DESCF_PARTITIONED : 0;
                 d.token = (uint64_t)(op - g_state->ops);
                 d.src_world = rank_;
@@ -804,6 +874,8 @@ int NativeTransport::progress_sends()
                         hipIpcMemHandle_t h;
                         if (hipIpcGetMemHandle(&h, base) != hipSuccess) {
                             MPIX_ERR("hipIpcGetMemHandle failed (buf %p)", base);
+                            /* the rest of a run fails the same way, op by
+                             * op, on the next turns of this loop */
                             op->ch_status.err = MPI_ERR_OTHER;
                             op->ch_done.store(1, std::memory_order_release);
                             q.pop_front();
@@ -814,9 +886,16 @@ int NativeTransport::progress_sends()
                     memcpy(d.ipc, &it->second.second, sizeof(hipIpcMemHandle_t));
                     d.ipc_off = (uint64_t)((char *)op->buf - (char *)base);
                 }
+                /* before the descriptor is visible: a self-loopback ack
+                 * comes back on this thread, another rank's through the
+                 * ring, both after this */
+                await_done_[d.token] = AwaitDone{
+                    op, op->req,
+                    RunAwait{op->partition, (uint32_t)k, (uint32_t)k}};
                 emit_desc(dst, d);
-                await_done_[d.token] = op;
-                q.pop_front();
+                g_state->notify_descs++;
+                g_state->notify_msgs += k;
+                q.erase(q.begin(), q.begin() + (long)k);
                 continue;
             }
             /* host-staged path */
@@ -889,24 +968,30 @@ int NativeTransport::drain_inbox(int src)
 void NativeTransport::handle_desc(int src, const Desc &d, const char *stage_base)
 {
     switch (d.type) {
-    case DESC_DONE: {
-        auto it = await_done_.find(d.token);
-        if (it == await_done_.end()) {
-            MPIX_ERR("DONE for unknown token %lu", (unsigned long)d.token);
-            return;
-        }
-        Op *op = it->second;
-        await_done_.erase(it);
-        complete_send_buffered(op);
+    case DESC_DONE:
+        handle_done(d.token, d.partition, d.count ? d.count : 1);
         return;
-    }
     case DESC_DEV_NOTIFY: {
-        inbound_.emplace_back();
-        InboundMsg &m = inbound_.back();
-        m.d = d;
-        m.src = src;
-        inbound_by_token_[((uint64_t)src << 32) ^ d.token] = &m;
-        try_match_new_inbound(m);
+        const uint32_t k = d.count ? d.count : 1;
+        if (k > 1 && try_run_fast_path(src, d, k)) return;
+        /* one message, or a run expanded in partition order exactly as if k
+         * descriptors had arrived: the ring position is the run's, so FIFO
+         * order per sender holds.  inbound_by_token_ is not written: only
+         * HOST_CHUNK descriptors look messages up by token. */
+        for (uint32_t j = 0; j < k; j++) {
+            inbound_.emplace_back();
+            InboundMsg &m = inbound_.back();
+            m.d = d; /* the ring slot is ours until drain_inbox moves tail */
+            m.src = src;
+            if (k > 1) {
+                const RunSlice sl = part_run_slice(
+                    d.partition, d.ipc_off, d.msg_bytes, d.token, j);
+                m.d.partition = sl.partition;
+                m.d.ipc_off = sl.ipc_off;
+                m.d.count = sl.count;
+            }
+            try_match_new_inbound(m);
+        }
         return;
     }
     case DESC_HOST_CHUNK: {
@@ -937,6 +1022,119 @@ void NativeTransport::handle_desc(int src, const Desc &d, const char *stage_base
     }
     default:
         MPIX_ERR("bad descriptor type %u from %d", d.type, src);
+    }
+}
+
+/* The sender's end of an ack: partitions [first, first+count) of the run
+ * announced under `token` (or the single message) are finished. */
+void NativeTransport::handle_done(uint64_t token, int32_t first,
+                                  uint32_t count)
+{
+    auto it = await_done_.find(token);
+    if (it == await_done_.end()) {
+        MPIX_ERR("DONE for unknown token %lu", (unsigned long)token);
+        return;
+    }
+    AwaitDone &a = it->second;
+    const RunAck r = part_run_ack(&a.run, first, count);
+    if (r == RUN_ACK_BAD) {
+        MPIX_ERR("DONE for partitions %d..+%u outside run %d..+%u (%u left) "
+                 "of token %lu", first, count, a.run.p0, a.run.k,
+                 a.run.remaining, (unsigned long)token);
+        return;
+    }
+    if (a.run.k == 1) {
+        complete_send_buffered(a.op);
+    } else {
+        for (uint32_t j = 0; j < count; j++)
+            complete_send_buffered(
+                &g_state->ops[a.req->part_idx[first + (int32_t)j]]);
+    }
+    if (r == RUN_ACK_LAST) await_done_.erase(it);
+}
+
+/* The receiver's end: tell rank `src` that partitions [first, first+count)
+ * under `token` are finished.  For ourselves the send ops complete right
+ * here: through the ring the DONE would be drained one proxy pass later
+ * (drain_inbox runs before progress_copies), and a wait on the send
+ * request that follows the wait on the receive sits through that pass. */
+void NativeTransport::ack(int src, uint64_t token, int32_t first,
+                          uint32_t count)
+{
+    if (src == rank_) {
+        handle_done(token, first, count);
+        return;
+    }
+    if (ring_has_space(src, 1)) {
+        Desc d;
+        d.type = DESC_DONE;
+        d.token = token;
+        d.src_world = rank_;
+        d.partition = first;
+        d.count = count;
+        emit_desc(src, d);
+    } else {
+        pending_done_.push_back(PendingDone{src, token, first, count});
+    }
+}
+
+/* A run of k partitions whose receives are all posted, in order, as slices
+ * of one device buffer (part_run_fast_range) is ONE pending pull of
+ * k * msg_bytes: no InboundMsg, one erase from posted_recvs_, one entry of
+ * the batch.  false: nothing was touched, the caller expands the run. */
+bool NativeTransport::try_run_fast_path(int src, const Desc &d, uint32_t k)
+{
+    if (!(d.flags & DESCF_PARTITIONED) || (d.flags & DESCF_STRIDED))
+        return false;
+    void *sp = map_remote(d);
+    if (sp == nullptr) return false; /* the expansion fails op by op */
+    const long first = part_run_fast_range(
+        posted_recvs_.size(),
+        [&](size_t i) {
+            const Op *o = posted_recvs_[i];
+            const bool env =
+                o->kind == OpKind::PRECV_PART && o->comm_id == d.comm_id &&
+                (o->peer_world == MPI_ANY_SOURCE || o->peer_world == src) &&
+                (o->tag == MPI_ANY_TAG || o->tag == d.tag);
+            return RunRecv{o->req, o->partition, o->bytes,
+                           (uintptr_t)o->buf, env, o->buf_is_device,
+                           o->strided};
+        },
+        d.partition, k, d.msg_bytes, (uintptr_t)sp);
+    if (first < 0) return false;
+    Op *op = posted_recvs_[(size_t)first];
+    /* the slices must be the request's own partitions: finish_pull finds
+     * receive j through op->req->part_idx */
+    const Request *rq = op->req;
+    if (rq == nullptr || d.partition < 0 ||
+        (uint64_t)d.partition + k > (uint64_t)rq->n_partitions)
+        return false;
+    posted_recvs_.erase(posted_recvs_.begin() + first,
+                        posted_recvs_.begin() + first + (long)k);
+    ChStatus st;
+    st.src = (op->comm_id == 1) ? 0 : src;
+    st.tag = d.tag;
+    st.bytes = d.msg_bytes;
+    st.err = MPI_SUCCESS;
+    uint64_t seen = op->t_issue_ns > d.t_seen_ns ? op->t_issue_ns
+                                                 : d.t_seen_ns;
+    pend_pulls_.push_back(PendingPull{op, src, d.token, st, op->buf, sp,
+                                      (uint64_t)k * d.msg_bytes, seen,
+                                      d.partition, k});
+    g_state->run_fast_msgs += k;
+    return true;
+}
+
+/* Every receive of a pull gets its status and ch_done (the per-partition
+ * flag transitions stay with the proxy walk); the sender gets ONE ack. */
+void NativeTransport::finish_pull(const PendingPull &pp, BatchStat *bs)
+{
+    ack(pp.src, pp.token, pp.partition, pp.k);
+    for (uint32_t j = 0; j < pp.k; j++) {
+        Op *op = pull_op(pp, j);
+        op->stat_batch = bs;
+        op->ch_status = pp.st;
+        op->ch_done.store(1, std::memory_order_release);
     }
 }
 
@@ -1041,7 +1239,9 @@ void *NativeTransport::map_remote(const Desc &d)
     if (d.flags & DESCF_SELF_PTR) {
         uint64_t p;
         memcpy(&p, d.ipc, 8);
-        return (void *)(uintptr_t)p;
+        /* the sender writes offset 0; slice j of an expanded run is at
+         * j * msg_bytes (part_run_slice) */
+        return (char *)(uintptr_t)p + d.ipc_off;
     }
     std::string key((const char *)d.ipc, sizeof(hipIpcMemHandle_t));
     auto it = ipc_open_.find(key);
@@ -1075,7 +1275,7 @@ void NativeTransport::start_dev_copy(InboundMsg &m)
         op->ch_status = st;
         op->ch_done.store(1, std::memory_order_release);
         /* still ack so the sender does not hang */
-        pending_done_.emplace_back(m.src, m.d.token);
+        ack(m.src, m.d.token, m.d.partition, 1);
         erase_inbound(&m);
         return;
     }
@@ -1088,7 +1288,7 @@ void NativeTransport::start_dev_copy(InboundMsg &m)
         st.err = MPI_ERR_TYPE;
         op->ch_status = st;
         op->ch_done.store(1, std::memory_order_release);
-        pending_done_.emplace_back(m.src, m.d.token);
+        ack(m.src, m.d.token, m.d.partition, 1);
         erase_inbound(&m);
         return;
     }
@@ -1100,7 +1300,8 @@ void NativeTransport::start_dev_copy(InboundMsg &m)
         uint64_t seen = op->t_issue_ns > m.d.t_seen_ns ? op->t_issue_ns
                                                        : m.d.t_seen_ns;
         PendingStrided ps;
-        ps.pp = PendingPull{op, m.src, m.d.token, st, op->buf, src, n, seen};
+        ps.pp = PendingPull{op, m.src, m.d.token, st, op->buf, src, n, seen,
+                            m.d.partition, 1};
         ps.sl = (m.d.flags & DESCF_STRIDED) ? m.d.layout
                                             : layout_contiguous(m.d.msg_bytes);
         ps.dl = op->strided ? op->layout : layout_contiguous(op->bytes);
@@ -1125,7 +1326,8 @@ void NativeTransport::start_dev_copy(InboundMsg &m)
         uint64_t seen = op->t_issue_ns > m.d.t_seen_ns ? op->t_issue_ns
                                                        : m.d.t_seen_ns;
         pend_pulls_.push_back(PendingPull{op, m.src, m.d.token, st,
-                                          op->buf, src, n, seen});
+                                          op->buf, src, n, seen,
+                                          m.d.partition, 1});
         m.dev_copy_started = true;
         erase_inbound(&m);
         return;
@@ -1140,7 +1342,7 @@ void NativeTransport::start_dev_copy(InboundMsg &m)
         st.err = MPI_ERR_OTHER;
         op->ch_status = st;
         op->ch_done.store(1, std::memory_order_release);
-        pending_done_.emplace_back(m.src, m.d.token);
+        ack(m.src, m.d.token, m.d.partition, 1);
         erase_inbound(&m);
         return;
     }
@@ -1151,7 +1353,8 @@ void NativeTransport::start_dev_copy(InboundMsg &m)
     hipError_t erec = hipEventRecord(ev, cs);
     if (erec != hipSuccess)
         MPIX_ERR("hipEventRecord(pull) failed: %s", hipGetErrorString(erec));
-    copies_.push_back(CopyInflight{op, ev, m.src, m.d.token, st});
+    copies_.push_back(CopyInflight{op, ev, m.src, m.d.token, m.d.partition,
+                                   st});
     m.dev_copy_started = true;
     erase_inbound(&m);
 }
@@ -1236,11 +1439,8 @@ void NativeTransport::flush_pulls()
         if (e != hipSuccess) {
             MPIX_ERR("k_pull_multi launch failed: %s", hipGetErrorString(e));
             for (size_t i = 0; i < n; i++) {
-                PendingPull &pp = pend_pulls_[i];
-                pp.st.err = MPI_ERR_OTHER;
-                pp.op->ch_status = pp.st;
-                pp.op->ch_done.store(1, std::memory_order_release);
-                pending_done_.emplace_back(pp.src, pp.token);
+                pend_pulls_[i].st.err = MPI_ERR_OTHER;
+                finish_pull(pend_pulls_[i], nullptr);
             }
             pend_pulls_.erase(pend_pulls_.begin(), pend_pulls_.begin() + n);
             continue;
@@ -1249,14 +1449,28 @@ void NativeTransport::flush_pulls()
         b.ev = get_event();
         (void)hipEventRecord(b.ev, cs);
         b.t_launch_ns = 0;
+        b.first = false;
         if (stats) {
+            State *s = g_state;
             b.t_launch_ns = now_ns();
-            g_state->bleg_wait_ns += b.t_launch_ns - t_first;
-            g_state->bleg_call_ns += t_rec - t_call;
-            g_state->bleg_rec_ns += b.t_launch_ns - t_rec;
-            g_state->bleg_n++;
-            g_state->bleg_items += n;
-            g_state->bleg_copies += plan_.ncopies;
+            const uint64_t call = t_rec - t_call;
+            if (!s->bleg_first_seen) {
+                /* loads the code object: reported apart from the means */
+                s->bleg_first_seen = b.first = true;
+                s->bleg_first_wait_ns = b.t_launch_ns - t_first;
+                s->bleg_first_call_ns = call;
+                s->bleg_first_rec_ns = b.t_launch_ns - t_rec;
+                s->bleg_first_items = pull_ops(pend_pulls_, n);
+            } else {
+                s->bleg_wait_ns += b.t_launch_ns - t_first;
+                s->bleg_call_ns += call;
+                if (call < s->bleg_call_min_ns) s->bleg_call_min_ns = call;
+                if (call > s->bleg_call_max_ns) s->bleg_call_max_ns = call;
+                s->bleg_rec_ns += b.t_launch_ns - t_rec;
+                s->bleg_n++;
+                s->bleg_items += pull_ops(pend_pulls_, n);
+                s->bleg_copies += plan_.ncopies;
+            }
         }
         b.items.assign(pend_pulls_.begin(), pend_pulls_.begin() + n);
         pend_pulls_.erase(pend_pulls_.begin(), pend_pulls_.begin() + n);
@@ -1296,11 +1510,8 @@ void NativeTransport::flush_strided()
         if (e != hipSuccess) {
             MPIX_ERR("k_pull_strided launch failed: %s", hipGetErrorString(e));
             for (size_t i = 0; i < n; i++) {
-                PendingPull &pp = pend_strided_[i].pp;
-                pp.st.err = MPI_ERR_OTHER;
-                pp.op->ch_status = pp.st;
-                pp.op->ch_done.store(1, std::memory_order_release);
-                pending_done_.emplace_back(pp.src, pp.token);
+                pend_strided_[i].pp.st.err = MPI_ERR_OTHER;
+                finish_pull(pend_strided_[i].pp, nullptr);
             }
             pend_strided_.erase(pend_strided_.begin(),
                                 pend_strided_.begin() + n);
@@ -1310,6 +1521,7 @@ void NativeTransport::flush_strided()
         b.ev = get_event();
         (void)hipEventRecord(b.ev, cs);
         b.t_launch_ns = 0; /* the batch legs of MPIX_STATS count plain pulls */
+        b.first = false;
         for (size_t i = 0; i < n; i++) b.items.push_back(pend_strided_[i].pp);
         pend_strided_.erase(pend_strided_.begin(), pend_strided_.begin() + n);
         batches_.push_back(std::move(b));
@@ -1331,23 +1543,17 @@ int NativeTransport::progress_copies()
         put_event(it->ev);
         BatchStat *bs = nullptr;
         if (it->t_launch_ns) {
-            bs = new BatchStat{now_ns(), (int)it->items.size()};
-            g_state->bleg_kernel_ns += bs->t_ev_ns - it->t_launch_ns;
+            bs = new BatchStat{now_ns(),
+                               (int)pull_ops(it->items, it->items.size()),
+                               it->first};
+            if (it->first)
+                g_state->bleg_first_kernel_ns = bs->t_ev_ns - it->t_launch_ns;
+            else
+                g_state->bleg_kernel_ns += bs->t_ev_ns - it->t_launch_ns;
         }
         for (PendingPull &pp : it->items) {
             if (e != hipSuccess) pp.st.err = MPI_ERR_OTHER;
-            pp.op->stat_batch = bs;
-            if (ring_has_space(pp.src, 1)) {
-                Desc d;
-                d.type = DESC_DONE;
-                d.token = pp.token;
-                d.src_world = rank_;
-                emit_desc(pp.src, d);
-            } else {
-                pending_done_.emplace_back(pp.src, pp.token);
-            }
-            pp.op->ch_status = pp.st;
-            pp.op->ch_done.store(1, std::memory_order_release);
+            finish_pull(pp, bs);
         }
         it = batches_.erase(it);
     }
@@ -1362,15 +1568,7 @@ int NativeTransport::progress_copies()
             fprintf(stderr, "[mpix trace] pull done (e=%d)\n", (int)e);
         put_event(it->ev);
         /* ack the sender, then complete the recv */
-        if (ring_has_space(it->src, 1)) {
-            Desc d;
-            d.type = DESC_DONE;
-            d.token = it->token;
-            d.src_world = rank_;
-            emit_desc(it->src, d);
-        } else {
-            pending_done_.emplace_back(it->src, it->token);
-        }
+        ack(it->src, it->token, it->partition, 1);
         it->op->ch_status = it->st;
         it->op->ch_done.store(1, std::memory_order_release);
         it = copies_.erase(it);
