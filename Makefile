@@ -41,7 +41,7 @@ $(PYEXT): mpix/_core.o $(OBJS)
 
 src/transport/native.o: src/transport/pull_plan.h src/transport/layout.h \
                         src/transport/strided_plan.h src/transport/part_run.h
-src/enqueue.o: src/transport/layout.h
+src/enqueue.o src/partitioned.o: src/transport/layout.h
 
 $(LIB): $(OBJS)
 	$(HIPCC) --offload-arch=$(GPU_ARCH) $(OBJS) $(LDFLAGS) -o $@

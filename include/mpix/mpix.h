@@ -87,8 +87,9 @@ int MPIX_Irecv_enqueue(void *buf, int count, MPI_Datatype datatype,
  * MPI_ERR_TYPE at enqueue for a communicator served by the MPI passthrough
  * transport, and as the completion status when one buffer is in device and
  * the other in host memory (plain messages between the two kinds work).
- * Not supported: partitioned requests with layouts, decoding
- * MPI_Type_vector / subarray handles, more than two strided levels. */
+ * Partitioned requests with layouts: MPIX_Psend/Precv_init_strided below.
+ * Not supported: decoding MPI_Type_vector / subarray handles, more than two
+ * strided levels. */
 int MPIX_Isend_strided_enqueue(const void *buf, const MPIX_Layout *layout,
                                int dest, int tag, MPI_Comm comm,
                                MPIX_Request *request, int qtype, void *queue);
@@ -111,6 +112,42 @@ int MPIX_Psend_init(const void *buf, int partitions, MPI_Count count,
 int MPIX_Precv_init(void *buf, int partitions, MPI_Count count,
                     MPI_Datatype datatype, int source, int tag, MPI_Comm comm,
                     MPI_Info info, MPIX_Request *request);
+
+/* Strided variants: partition p is the buffer at buf + p * part_stride laid
+ * out as *part_layout (mpix_layout.h), and its message is that layout's
+ * bytes in (plane, run, byte) order: a y-face of a grid split along z, a
+ * column block of a matrix, rows of a pitched allocation, published slab by
+ * slab without a pack kernel.  As with the strided enqueue calls only the
+ * byte sequence of a partition has to agree between the two sides: each may
+ * use the plain init call, a strided one, or a differently strided one.
+ * Everything that takes the request (MPIX_Start, MPIX_Pready, MPIX_Parrived,
+ * MPIX_Wait, MPIX_Prequest_create and the __device__ functions, reuse across
+ * iterations, MPIX_Request_free) is the same call and behaves the same.  A
+ * contiguous layout with part_stride equal to its bytes IS the plain call.
+ * Device partitions made ready together are announced as a run and moved by
+ * one kernel entry: as one strided message when the run folds into a layout
+ * on both sides, by the kernel's partition level otherwise; host partitions
+ * are staged one by one.
+ * Errors, all at init: MPI_ERR_ARG for a null or illegal layout (as for the
+ * enqueue calls) and, with more than one partition, a part_stride that is
+ * zero, negative, smaller than the layout's extent (partitions would
+ * overlap) or so large that the whole buffer overflows 63 bits;
+ * MPI_ERR_TYPE for a communicator or peer served by the MPI passthrough
+ * transport and under MPIX_MPI_PARTITIONED=1.  A strided partition between
+ * device and host memory completes with MPI_ERR_TYPE, as a strided message.
+ * Not supported: partitions of unequal size, a layout per partition, more
+ * than two strided levels inside a partition. */
+int MPIX_Psend_init_strided(const void *buf, int partitions,
+                            const MPIX_Layout *part_layout,
+                            int64_t part_stride, int dest, int tag,
+                            MPI_Comm comm, MPI_Info info,
+                            MPIX_Request *request);
+
+int MPIX_Precv_init_strided(void *buf, int partitions,
+                            const MPIX_Layout *part_layout,
+                            int64_t part_stride, int source, int tag,
+                            MPI_Comm comm, MPI_Info info,
+                            MPIX_Request *request);
 
 /* Build a device-resident handle for __device__ MPIX_Pready/Parrived. */
 int MPIX_Prequest_create(MPIX_Request request, MPIX_Prequest *prequest);

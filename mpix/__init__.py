@@ -224,16 +224,70 @@ def request_free(req):
 
 # ----------------------------- partitioned --------------------------------
 
+def _is_view(buf):
+    """A non-empty tensor / ndarray that is not C-contiguous."""
+    if hasattr(buf, "data_ptr"):
+        return buf.numel() > 0 and not buf.is_contiguous()
+    if hasattr(buf, "ctypes"):
+        return buf.size > 0 and not buf.flags["C_CONTIGUOUS"]
+    return False
+
+
+def _pinit(is_send, buf, partitions, peer, tag, nbytes):
+    """Contiguous buffers and (addr, nbytes) tuples take the plain bindings;
+    a non-contiguous view is split along dimension 0 into partitions that
+    are laid out alike."""
+    if not _is_view(buf):
+        addr, n = _addr_len(buf, nbytes)
+        assert n % partitions == 0, "buffer must divide evenly into partitions"
+        f = _C.psend_init if is_send else _C.precv_init
+        return f(addr, partitions, n // partitions, peer, tag)
+    if nbytes is not None:
+        raise ValueError("nbytes= cannot be combined with a non-contiguous "
+                         "buffer: the view defines the partitions")
+    shape = tuple(buf.shape)
+    if hasattr(buf, "data_ptr"):
+        item = buf.element_size()
+        strides = tuple(s * item for s in buf.stride())
+        addr = buf.data_ptr()
+    else:
+        item = buf.itemsize
+        strides = tuple(buf.strides)
+        addr = buf.ctypes.data
+    if partitions <= 0 or shape[0] % partitions != 0:
+        raise ValueError(
+            f"cannot split a view of shape {shape} into {partitions} "
+            f"partitions: they split dimension 0, which must divide evenly")
+    rows = shape[0] // partitions
+    part_stride = rows * strides[0]
+    if partitions > 1 and part_stride <= 0:
+        raise ValueError(
+            f"cannot send/receive a view of shape {shape} with byte strides "
+            f"{strides} as partitions: zero or negative strides (expand, "
+            f"flip) are not supported")
+    part = buf[:rows]
+    lay = _layout_of(part)  # ValueError for what does not fit a layout
+    if lay is None:  # one partition of the view is contiguous
+        n = rows * item
+        for size in shape[1:]:
+            n *= size
+        layout = (n, 1, 1, n, n)
+    else:
+        layout = lay[1]
+    return _C.psend_precv_init_strided(is_send, int(addr), partitions,
+                                       *layout, int(part_stride), peer, tag)
+
+
 def psend_init(buf, partitions, dest, tag=0, nbytes=None):
-    addr, n = _addr_len(buf, nbytes)
-    assert n % partitions == 0, "buffer must divide evenly into partitions"
-    return _C.psend_init(addr, partitions, n // partitions, dest, tag)
+    """Partitioned send of `buf`: a contiguous tensor / ndarray or an
+    (address, nbytes) pair cut into `partitions` equal slices, or a
+    non-contiguous view whose dimension 0 is split into `partitions` equal
+    slabs (each one partition, sent in C order without packing)."""
+    return _pinit(True, buf, partitions, dest, tag, nbytes)
 
 
 def precv_init(buf, partitions, source, tag=0, nbytes=None):
-    addr, n = _addr_len(buf, nbytes)
-    assert n % partitions == 0, "buffer must divide evenly into partitions"
-    return _C.precv_init(addr, partitions, n // partitions, source, tag)
+    return _pinit(False, buf, partitions, source, tag, nbytes)
 
 
 def start(req):

@@ -284,6 +284,39 @@ PYBIND11_MODULE(_C, m)
         return r;
     }, py::return_value_policy::take_ownership);
 
+    /* strided variant of both: partition p is the buffer at
+     * buf + p * part_stride laid out as (run_bytes, count0, count1, stride0,
+     * stride1), derived from the view in mpix/__init__.py */
+    m.def("psend_precv_init_strided",
+          [](bool is_send, uintptr_t buf, int partitions, uint64_t run_bytes,
+             uint64_t count0, uint64_t count1, int64_t stride0,
+             int64_t stride1, int64_t part_stride, int peer, int tag) {
+              MPIX_Layout l;
+              l.run_bytes = run_bytes;
+              l.count[0] = count0;
+              l.count[1] = count1;
+              l.stride[0] = stride0;
+              l.stride[1] = stride1;
+              auto *r = new MxRequest();
+              int rc = is_send
+                  ? MPIX_Psend_init_strided((const void *)buf, partitions, &l,
+                                            part_stride, peer, tag,
+                                            MPI_COMM_WORLD, MPI_INFO_NULL,
+                                            &r->req)
+                  : MPIX_Precv_init_strided((void *)buf, partitions, &l,
+                                            part_stride, peer, tag,
+                                            MPI_COMM_WORLD, MPI_INFO_NULL,
+                                            &r->req);
+              if (rc != 0) {
+                  delete r;
+                  throw std::runtime_error(
+                      "MPIX_P" + std::string(is_send ? "send" : "recv") +
+                      "_init_strided failed, rc=" + std::to_string(rc));
+              }
+              return r;
+          },
+          py::return_value_policy::take_ownership);
+
     m.def("start", [](MxRequest *r) { PY_CHECK(MPIX_Start(&r->req)); });
     m.def("pready", [](int partition, MxRequest *r) {
         PY_CHECK(MPIX_Pready(partition, (void *)r->req));

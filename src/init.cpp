@@ -633,6 +633,13 @@ extern "C" int MPIX_Finalize(void)
                     (unsigned long)s->notify_descs,
                     (unsigned long)s->notify_msgs,
                     (unsigned long)s->run_fast_msgs);
+        if (s->run_fast_msgs)
+            fprintf(stderr,
+                    "[mpix stats r%d] fast runs: %lu as one contiguous copy, "
+                    "%lu folded into one strided entry, %lu as an entry "
+                    "with a partition level\n", s->world_rank,
+                    (unsigned long)s->run_copy, (unsigned long)s->run_folded,
+                    (unsigned long)s->run_parts);
         if (s->bleg_first_seen) {
             /* on its own line and in none of the means below: this launch
              * loads the code object */

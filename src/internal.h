@@ -139,8 +139,9 @@ struct Op {
     bool buf_is_device = false;
     bool native_route = true;       /* native shm/xGMI channel vs MPI passthrough */
     int partition = -1;             /* >=0 for partitioned partial ops */
-    /* strided enqueue (MPIX_I*_strided_enqueue): buf is laid out as `layout`
-     * (normalised, not contiguous) and `bytes` is the message length */
+    /* strided enqueue (MPIX_I*_strided_enqueue) or strided partition
+     * (MPIX_P*_init_strided): buf is laid out as `layout` (normalised, not
+     * contiguous) and `bytes` is the message length */
     bool strided = false;
     MPIX_Layout layout = {};
     uint32_t pseq = 0;              /* partitioned iteration number */
@@ -210,7 +211,11 @@ struct Request {
     int n_partitions = 0;
     std::vector<int> part_idx;      /* partition -> flag slot */
     void *buf = nullptr;
-    uint64_t part_bytes = 0;        /* bytes per partition */
+    uint64_t part_bytes = 0;        /* message bytes per partition */
+    /* partition p starts at buf + p * part_stride: part_bytes for the plain
+     * init calls, the caller's for MPIX_P*_init_strided.  The transport's
+     * run code reads THIS, never part_bytes. */
+    int64_t part_stride = 0;
     int peer = -1, peer_world = -1, tag = 0;
     MPI_Comm comm = MPI_COMM_NULL;
     uint32_t comm_id = 0;
@@ -361,6 +366,9 @@ struct State {
      * k partitions is one descriptor, part_run.h); messages received on the
      * fast path of a run.  Proxy thread only, counted always. */
     uint64_t notify_descs = 0, notify_msgs = 0, run_fast_msgs = 0;
+    /* runs taken on the fast path, by the pull they became: one contiguous
+     * copy, one folded strided entry, one entry with a partition level */
+    uint64_t run_copy = 0, run_folded = 0, run_parts = 0;
     bool bleg_first_seen = false;
     uint64_t bleg_first_wait_ns = 0, bleg_first_call_ns = 0;
     uint64_t bleg_first_rec_ns = 0, bleg_first_kernel_ns = 0;

@@ -20,19 +20,58 @@
 #include <hip/hip_runtime.h>
 
 #include "internal.h"
+#include "transport/layout.h"
 
 namespace mpix {
 
+/* Common body of the plain and the strided init calls.  `layout` non-null
+ * (the strided calls): count and datatype are ignored, partition p is the
+ * buffer at buf + p * part_stride laid out as *layout. */
 static int psend_precv_init(bool is_send, void *buf, int partitions,
                             MPI_Count count, MPI_Datatype datatype, int peer,
-                            int tag, MPI_Comm comm, MPIX_Request *request)
+                            int tag, MPI_Comm comm, MPIX_Request *request,
+                            const MPIX_Layout *layout = nullptr,
+                            int64_t part_stride = 0)
 {
     State *s = g_state;
     if (s == nullptr) return MPI_ERR_OTHER;
     if (request == nullptr || partitions <= 0 || count < 0) return MPI_ERR_ARG;
 
     int tsz = 0;
-    MPIX_CHECK(datatype_size(datatype, &tsz));
+    MPIX_Layout norm = {};
+    if (layout != nullptr) {
+        /* everything is checked here, before any slot is allocated */
+        uint64_t extent = 0;
+        if (layout_validate(*layout, &extent) != 0) {
+            MPIX_ERR("invalid partition layout: run %lu, counts %lu %lu, "
+                     "strides %ld %ld (strides must be positive and not "
+                     "smaller than what they step over)",
+                     (unsigned long)layout->run_bytes,
+                     (unsigned long)layout->count[0],
+                     (unsigned long)layout->count[1], (long)layout->stride[0],
+                     (long)layout->stride[1]);
+            return MPI_ERR_ARG;
+        }
+        if (partitions > 1) {
+            int64_t span;
+            if (part_stride <= 0 || (uint64_t)part_stride < extent ||
+                !layout_muladd(part_stride, (uint64_t)partitions - 1, extent,
+                               &span)) {
+                MPIX_ERR("invalid part_stride %ld for %d partitions of extent "
+                         "%lu: it must be positive, not smaller than the "
+                         "extent (partitions would overlap), and the whole "
+                         "must fit 63 bits", (long)part_stride, partitions,
+                         (unsigned long)extent);
+                return MPI_ERR_ARG;
+            }
+        }
+        norm = layout_normalize(*layout);
+        datatype = MPI_BYTE;
+        tsz = 1;
+        count = (MPI_Count)layout_bytes(norm);
+    } else {
+        MPIX_CHECK(datatype_size(datatype, &tsz));
+    }
     int peer_world = -1;
     uint32_t comm_id = 0;
     bool native_ok = false;
@@ -55,6 +94,12 @@ static int psend_precv_init(bool is_send, void *buf, int partitions,
         mpi_native = want && s->mpi_mode;
     }
 #endif
+    if (layout != nullptr && (!native_ok || mpi_native)) {
+        MPIX_ERR("strided partitions are served by the native transport only; "
+                 "this communicator or the MPI-4.0 passthrough "
+                 "(MPIX_MPI_PARTITIONED=1) is routed through MPI");
+        return MPI_ERR_TYPE;
+    }
     if (!native_ok && !s->mpi_mode) {
         MPIX_ERR("partitioned ops on non-WORLD/SELF comms require MPI mode");
         return MPI_ERR_COMM;
@@ -67,6 +112,8 @@ static int psend_precv_init(bool is_send, void *buf, int partitions,
     req->part_idx.resize(partitions);
     req->buf = buf;
     req->part_bytes = (uint64_t)count * (uint64_t)tsz;
+    req->part_stride =
+        layout != nullptr ? part_stride : (int64_t)req->part_bytes;
     req->peer = peer;
     req->peer_world = peer_world;
     req->tag = tag;
@@ -106,7 +153,7 @@ static int psend_precv_init(bool is_send, void *buf, int partitions,
         req->part_idx[p] = idx;
         Op *op = &s->ops[idx];
         op->kind = is_send ? OpKind::PSEND_PART : OpKind::PRECV_PART;
-        op->buf = (char *)buf + (uint64_t)p * req->part_bytes;
+        op->buf = (char *)buf + (int64_t)p * req->part_stride;
         op->count = (int)count;
         op->datatype = datatype;
         op->bytes = req->part_bytes;
@@ -116,12 +163,17 @@ static int psend_precv_init(bool is_send, void *buf, int partitions,
         op->comm = comm;
         op->comm_id = comm_id;
         op->partition = p;
+        if (layout != nullptr) {
+            /* a layout that is really contiguous is a plain partition */
+            op->strided = !layout_is_contiguous(norm);
+            op->layout = norm;
+        }
         /* native shm/xGMI for WORLD/SELF; MPI transport for arbitrary comms
          * (header-routed partition messages) and the MPI-4.0 passthrough */
         op->native_route = native_ok && !req->mpi_part_native;
         op->req = req;
     }
-    /* buffer kind determined once (partitions are slices of one buffer) */
+    /* buffer kind determined once (partitions are pieces of one buffer) */
     bool dev = ptr_is_device(buf);
     for (int p = 0; p < partitions; p++)
         s->ops[req->part_idx[p]].buf_is_device = dev;
@@ -148,6 +200,30 @@ extern "C" int MPIX_Precv_init(void *buf, int partitions, MPI_Count count,
     (void)info;
     return psend_precv_init(false, buf, partitions, count, datatype, source,
                             tag, comm, request);
+}
+
+extern "C" int MPIX_Psend_init_strided(const void *buf, int partitions,
+                                       const MPIX_Layout *part_layout,
+                                       int64_t part_stride, int dest, int tag,
+                                       MPI_Comm comm, MPI_Info info,
+                                       MPIX_Request *request)
+{
+    (void)info;
+    if (part_layout == nullptr) return MPI_ERR_ARG;
+    return psend_precv_init(true, (void *)buf, partitions, 0, MPI_BYTE, dest,
+                            tag, comm, request, part_layout, part_stride);
+}
+
+extern "C" int MPIX_Precv_init_strided(void *buf, int partitions,
+                                       const MPIX_Layout *part_layout,
+                                       int64_t part_stride, int source,
+                                       int tag, MPI_Comm comm, MPI_Info info,
+                                       MPIX_Request *request)
+{
+    (void)info;
+    if (part_layout == nullptr) return MPI_ERR_ARG;
+    return psend_precv_init(false, buf, partitions, 0, MPI_BYTE, source, tag,
+                            comm, request, part_layout, part_stride);
 }
 
 extern "C" int MPIX_Start(MPIX_Request *reqp)

@@ -135,6 +135,61 @@ static inline int64_t layout_offset(const MPIX_Layout &l, uint64_t pos)
     return off;
 }
 
+/* The same for a run of partitions: partition q is laid out as `l` at
+ * q * part_stride, and the run's message is the partitions' messages one
+ * after the other.  Byte offset from the first partition's buffer of message
+ * position `pos` (< k * layout_bytes(l), layout_bytes(l) > 0).  THE
+ * definition for everything that treats several partitions as one transfer:
+ * part_layout_fold, the partition level of k_pull_strided, the expansion of
+ * a run descriptor. */
+static inline int64_t part_layout_offset(const MPIX_Layout &l,
+                                         int64_t part_stride, uint64_t pos)
+{
+    const uint64_t pb = layout_bytes(l);
+    const uint64_t q = pos / pb;
+    return (int64_t)q * part_stride + layout_offset(l, pos - q * pb);
+}
+
+/* k partitions laid out as the NORMALISED layout `l`, part_stride apart, as
+ * ONE layout: (k, part_stride) is a third, outermost level.  It folds when it
+ * adds no level of its own to a strided partition: the partitions continue
+ * the outermost level of `l` at its pitch (a y-face split along z:
+ * part_stride == count[0] * stride[0]; with planes, count[1] * stride[1]), or
+ * `l` is contiguous and the partitions become its only level (rows with a
+ * gap; no gap: one run).  Anything else is refused, also a one-level layout
+ * with an unrelated part stride, which MPIX_Layout could hold as planes: the
+ * run then goes to the kernel variant with a partition level, and what folds
+ * costs exactly what the same bytes cost as one plain strided message.
+ * true: *out is normalised and layout_offset(*out, pos) ==
+ * part_layout_offset(l, part_stride, pos) for every pos.  k == 1 folds to
+ * `l`.  Needs layout_bytes(l) > 0 and part_stride >= the extent of `l`. */
+static inline bool part_layout_fold(const MPIX_Layout &l, uint64_t k,
+                                    int64_t part_stride, MPIX_Layout *out)
+{
+    if (k == 0 || layout_bytes(l) == 0) return false;
+    if (k == 1) {
+        *out = l;
+        return true;
+    }
+    if (part_stride <= 0) return false;
+    MPIX_Layout o = l;
+    if (l.count[1] > 1) {
+        if ((uint64_t)part_stride != l.count[1] * (uint64_t)l.stride[1])
+            return false;
+        o.count[1] = l.count[1] * k;
+    } else if (l.count[0] > 1) {
+        if ((uint64_t)part_stride != l.count[0] * (uint64_t)l.stride[0])
+            return false;
+        o.count[0] = l.count[0] * k;
+    } else {
+        if ((uint64_t)part_stride < l.run_bytes) return false;
+        o.count[0] = k;
+        o.stride[0] = part_stride;
+    }
+    *out = layout_normalize(o);
+    return true;
+}
+
 /* Shared walk of message bytes [pos, pos + n): calls f(buffer_offset,
  * message_offset_from_pos, len) once per (piece of a) run. */
 template <typename F>
@@ -180,14 +235,19 @@ static inline uint64_t layout_align_bits(const MPIX_Layout &l, uint64_t base)
     return bits;
 }
 
-/* Largest power of two <= 16 that divides both runs, all strides in use and
- * both base addresses: every unit of that size at a message position that
+/* Largest power of two <= 16 that divides both runs, all strides in use,
+ * both base addresses and, for a run of partitions, both part strides (0
+ * when there is no partition level): every unit of that size at a message position that
  * is a multiple of it lies inside one run on both sides, aligned.  16 selects
  * the vector path of k_pull_strided, 8/4/2/1 its element path. */
 static inline uint32_t layout_granule(const MPIX_Layout &a, uint64_t base_a,
-                                      const MPIX_Layout &b, uint64_t base_b)
+                                      const MPIX_Layout &b, uint64_t base_b,
+                                      int64_t part_stride_a = 0,
+                                      int64_t part_stride_b = 0)
 {
     uint64_t bits = layout_align_bits(a, base_a) | layout_align_bits(b, base_b);
+    /* a run of partitions: every partition has to start aligned too */
+    bits |= (uint64_t)part_stride_a | (uint64_t)part_stride_b;
     uint32_t g = 16;
     while (g > 1 && (bits & (g - 1)) != 0) g >>= 1;
     return g;

@@ -148,8 +148,14 @@ __global__ __launch_bounds__(PULL_THREADS) void k_pull_multi(const PullTable t)
  * rounds of it per tile.  Every unit is bounds-checked against the entry
  * (the partial last tile takes the same code).  WIDE is the variant with
  * 64-bit division, launched only when an entry has 2^31 units or more: it
- * is many times the code, so the common kernel does not carry it. */
-template <typename T, int ROUNDS, bool WIDE>
+ * is many times the code, so the common kernel does not carry it.  PARTS is
+ * the variant for runs of partitions (an entry of k partitions, part strides
+ * apart on each side): one more division per unit splits off the partition
+ * number, shared by both sides since partitions have one size.  It is right
+ * for every entry (one without a partition level has a quotient of 0), and
+ * launched only when a batch holds a run entry, so plain strided messages
+ * do not pay the third division. */
+template <typename T, int ROUNDS, bool WIDE, bool PARTS>
 static __device__ __forceinline__ void strided_tile(const StridedEntry &e,
                                                     uint64_t unit0)
 {
@@ -157,6 +163,7 @@ static __device__ __forceinline__ void strided_tile(const StridedEntry &e,
     typedef __attribute__((address_space(1))) T *gdst;
     constexpr int U = MPIX_STRIDED_UNROLL;
     constexpr bool wide = WIDE;
+    constexpr bool parts = PARTS;
 #pragma unroll 1
     for (int j = 0; j < ROUNDS; j++) {
         T r[U];
@@ -168,9 +175,9 @@ static __device__ __forceinline__ void strided_tile(const StridedEntry &e,
                 (uint64_t)(j * U + k) * PULL_THREADS + threadIdx.x;
             ok[k] = u < e.units;
             if (ok[k]) {
-                r[k] = __builtin_nontemporal_load(
-                    (gsrc)(e.src + strided_side_offset(e.s, u, e.glog, wide)));
-                doff[k] = strided_side_offset(e.d, u, e.glog, wide);
+                int64_t soff;
+                strided_entry_offsets(e, u, wide, parts, &soff, &doff[k]);
+                r[k] = __builtin_nontemporal_load((gsrc)(e.src + soff));
             }
         }
 #pragma unroll
@@ -180,7 +187,7 @@ static __device__ __forceinline__ void strided_tile(const StridedEntry &e,
     }
 }
 
-template <bool WIDE>
+template <bool WIDE, bool PARTS>
 __global__ __launch_bounds__(PULL_THREADS) void k_pull_strided(
     const StridedTable t)
 {
@@ -199,11 +206,11 @@ __global__ __launch_bounds__(PULL_THREADS) void k_pull_strided(
         /* units of this tile start at (tile bytes) >> glog */
         const uint64_t unit0 = ((tile - first) * MPIX_STRIDED_TILE) >> cur.glog;
         switch (cur.glog) {
-        case 4: strided_tile<pull_v4, 1, WIDE>(cur, unit0); break;
-        case 3: strided_tile<uint64_t, 2, WIDE>(cur, unit0); break;
-        case 2: strided_tile<uint32_t, 4, WIDE>(cur, unit0); break;
-        case 1: strided_tile<uint16_t, 8, WIDE>(cur, unit0); break;
-        default: strided_tile<uint8_t, 16, WIDE>(cur, unit0); break;
+        case 4: strided_tile<pull_v4, 1, WIDE, PARTS>(cur, unit0); break;
+        case 3: strided_tile<uint64_t, 2, WIDE, PARTS>(cur, unit0); break;
+        case 2: strided_tile<uint32_t, 4, WIDE, PARTS>(cur, unit0); break;
+        case 1: strided_tile<uint16_t, 8, WIDE, PARTS>(cur, unit0); break;
+        default: strided_tile<uint8_t, 16, WIDE, PARTS>(cur, unit0); break;
         }
     }
 }
@@ -277,15 +284,23 @@ struct alignas(64) Desc {
     uint32_t comm_id = 0;
     int32_t partition = -1;   /* a run (count > 1): its first partition */
     uint64_t msg_bytes = 0;   /* a run: the size of ONE partition */
-    uint64_t chunk_off = 0;   /* HOST_CHUNK: offset of this chunk in the msg */
+    union {
+        uint64_t chunk_off = 0; /* HOST_CHUNK: offset of this chunk in the
+                                   msg */
+        int64_t part_stride;  /* DEV_NOTIFY of a partition: bytes between
+                                 partition p and p+1 at the SENDER (the
+                                 request's; not msg_bytes when there are
+                                 gaps).  Shares the word: a notify has no
+                                 chunks. */
+    };
     uint64_t chunk_bytes = 0;
     uint64_t stage_chunk = 0; /* HOST_CHUNK: chunk index in the stage ring */
     uint8_t ipc[64] = {};     /* DEV_NOTIFY: hipIpcMemHandle_t (or raw ptr) */
     uint64_t ipc_off = 0;
     int32_t src_dev = -1;
     uint32_t count = 0;       /* DEV_NOTIFY: partitions partition ..
-                                 partition+count-1 of one request, slices of
-                                 one buffer msg_bytes apart (part_run.h);
+                                 partition+count-1 of one request, laid out
+                                 alike, part_stride apart (part_run.h);
                                  DONE: that many partitions from `partition`
                                  on are finished.  0 reads as 1. */
     uint64_t t_seen_ns = 0;   /* DEV_NOTIFY: sender saw PENDING (MPIX_STATS=1;
@@ -449,6 +464,11 @@ private:
     struct PendingStrided {
         PendingPull pp;
         MPIX_Layout sl, dl; /* normalised source / destination layouts */
+        /* a run that did not fold: pp.k partitions laid out as sl / dl,
+         * these many bytes apart (parts false: one message, or a folded
+         * run whose sl / dl already span all of pp.n) */
+        bool parts = false;
+        int64_t s_part_stride = 0, d_part_stride = 0;
     };
     std::vector<PendingStrided> pend_strided_;
     StridedTable splan_{}; /* scratch of flush_strided; passed by value */
@@ -832,8 +852,7 @@ int NativeTransport::progress_sends()
                  * as ONE descriptor (part_run.h); anything else is a run
                  * of 1, today's descriptor */
                 size_t k = 1;
-                if (op->kind == OpKind::PSEND_PART && !op->strided &&
-                    part_runs_on())
+                if (op->kind == OpKind::PSEND_PART && part_runs_on())
                     k = part_run_length(q.size(), [&q](size_t i) {
                         const Op *o = q[i].op;
                         return RunSend{o->req, o->pseq, o->partition,
@@ -853,6 +872,10 @@ int NativeTransport::progress_sends()
                 d.msg_bytes = op->bytes;
                 d.src_dev = dev_;
                 d.t_seen_ns = op->t_issue_ns;
+                /* the request's, never inferred from msg_bytes: contiguous
+                 * partitions may have gaps between them */
+                if (op->kind == OpKind::PSEND_PART && op->req != nullptr)
+                    d.part_stride = op->req->part_stride;
                 if (op->strided) {
                     d.flags |= DESCF_STRIDED;
                     d.layout = op->layout;
@@ -984,8 +1007,11 @@ void NativeTransport::handle_desc(int src, const Desc &d, const char *stage_base
             m.d = d; /* the ring slot is ours until drain_inbox moves tail */
             m.src = src;
             if (k > 1) {
+                /* slice j starts j * (the sender's part_stride) further on;
+                 * layout and DESCF_STRIDED stay as the run had them */
                 const RunSlice sl = part_run_slice(
-                    d.partition, d.ipc_off, d.msg_bytes, d.token, j);
+                    d.partition, d.ipc_off, (uint64_t)d.part_stride, d.token,
+                    j);
                 m.d.partition = sl.partition;
                 m.d.ipc_off = sl.ipc_off;
                 m.d.count = sl.count;
@@ -1078,14 +1104,21 @@ void NativeTransport::ack(int src, uint64_t token, int32_t first,
     }
 }
 
-/* A run of k partitions whose receives are all posted, in order, as slices
- * of one device buffer (part_run_fast_range) is ONE pending pull of
- * k * msg_bytes: no InboundMsg, one erase from posted_recvs_, one entry of
- * the batch.  false: nothing was touched, the caller expands the run. */
+/* A run of k partitions whose receives are all posted, in order, as the
+ * partitions of one request in device memory (part_run_fast_range) is ONE
+ * pending pull: no InboundMsg, one erase from posted_recvs_, one entry of a
+ * batch.  Which pull is decided by the shape of both sides:
+ *  - contiguous partitions msg_bytes apart on both sides, both bases
+ *    16-byte aligned: one copy of k * msg_bytes (k_pull_multi);
+ *  - the run folds into a layout on each side (part_layout_fold: rows with
+ *    a gap, a face split along its outer dimension): one ordinary strided
+ *    entry, as if the k partitions were one strided message;
+ *  - anything else: a strided entry with a partition level.
+ * The last two go by the granule; only the first asks for alignment.
+ * false: nothing was touched, the caller expands the run. */
 bool NativeTransport::try_run_fast_path(int src, const Desc &d, uint32_t k)
 {
-    if (!(d.flags & DESCF_PARTITIONED) || (d.flags & DESCF_STRIDED))
-        return false;
+    if (!(d.flags & DESCF_PARTITIONED)) return false;
     void *sp = map_remote(d);
     if (sp == nullptr) return false; /* the expansion fails op by op */
     const long first = part_run_fast_range(
@@ -1096,18 +1129,29 @@ bool NativeTransport::try_run_fast_path(int src, const Desc &d, uint32_t k)
                 o->kind == OpKind::PRECV_PART && o->comm_id == d.comm_id &&
                 (o->peer_world == MPI_ANY_SOURCE || o->peer_world == src) &&
                 (o->tag == MPI_ANY_TAG || o->tag == d.tag);
-            return RunRecv{o->req, o->partition, o->bytes,
-                           (uintptr_t)o->buf, env, o->buf_is_device,
-                           o->strided};
+            RunRecv r{o->req, o->partition, o->bytes, (uintptr_t)o->buf, env,
+                      o->buf_is_device, o->strided};
+            /* the receiver's own distance between partitions */
+            r.part_stride = o->req != nullptr ? o->req->part_stride
+                                              : (int64_t)o->bytes;
+            return r;
         },
-        d.partition, k, d.msg_bytes, (uintptr_t)sp);
+        d.partition, k, d.msg_bytes);
     if (first < 0) return false;
     Op *op = posted_recvs_[(size_t)first];
-    /* the slices must be the request's own partitions: finish_pull finds
+    /* the receives must be the request's own partitions: finish_pull finds
      * receive j through op->req->part_idx */
     const Request *rq = op->req;
     if (rq == nullptr || d.partition < 0 ||
         (uint64_t)d.partition + k > (uint64_t)rq->n_partitions)
+        return false;
+    const bool s_strided = (d.flags & DESCF_STRIDED) != 0;
+    const bool plain = !s_strided && !op->strided &&
+                       d.part_stride == (int64_t)d.msg_bytes &&
+                       rq->part_stride == (int64_t)d.msg_bytes;
+    /* today's run, and today's rule for it: a misaligned one expands into
+     * k hipMemcpyAsync */
+    if (plain && ((((uintptr_t)op->buf) | ((uintptr_t)sp)) & 15) != 0)
         return false;
     posted_recvs_.erase(posted_recvs_.begin() + first,
                         posted_recvs_.begin() + first + (long)k);
@@ -1118,10 +1162,30 @@ bool NativeTransport::try_run_fast_path(int src, const Desc &d, uint32_t k)
     st.err = MPI_SUCCESS;
     uint64_t seen = op->t_issue_ns > d.t_seen_ns ? op->t_issue_ns
                                                  : d.t_seen_ns;
-    pend_pulls_.push_back(PendingPull{op, src, d.token, st, op->buf, sp,
-                                      (uint64_t)k * d.msg_bytes, seen,
-                                      d.partition, k});
+    const PendingPull pp{op, src, d.token, st, op->buf, sp,
+                         (uint64_t)k * d.msg_bytes, seen, d.partition, k};
     g_state->run_fast_msgs += k;
+    if (plain) {
+        pend_pulls_.push_back(pp);
+        g_state->run_copy++;
+        return true;
+    }
+    PendingStrided ps;
+    ps.pp = pp;
+    const MPIX_Layout sl =
+        s_strided ? d.layout : layout_contiguous(d.msg_bytes);
+    const MPIX_Layout dl =
+        op->strided ? op->layout : layout_contiguous(op->bytes);
+    if (!part_layout_fold(sl, k, d.part_stride, &ps.sl) ||
+        !part_layout_fold(dl, k, rq->part_stride, &ps.dl)) {
+        ps.sl = sl;
+        ps.dl = dl;
+        ps.parts = true;
+        ps.s_part_stride = d.part_stride;
+        ps.d_part_stride = rq->part_stride;
+    }
+    (ps.parts ? g_state->run_parts : g_state->run_folded)++;
+    pend_strided_.push_back(ps);
     return true;
 }
 
@@ -1240,7 +1304,7 @@ void *NativeTransport::map_remote(const Desc &d)
         uint64_t p;
         memcpy(&p, d.ipc, 8);
         /* the sender writes offset 0; slice j of an expanded run is at
-         * j * msg_bytes (part_run_slice) */
+         * j * part_stride (part_run_slice) */
         return (char *)(uintptr_t)p + d.ipc_off;
     }
     std::string key((const char *)d.ipc, sizeof(hipIpcMemHandle_t));
@@ -1492,6 +1556,11 @@ void NativeTransport::flush_strided()
         for (size_t i = 0; i < n; i++) {
             const PendingStrided &ps = pend_strided_[i];
             segs[i] = StridedSeg{ps.pp.dst, ps.pp.csrc, ps.pp.n, ps.sl, ps.dl};
+            if (ps.parts) {
+                segs[i].parts = ps.pp.k;
+                segs[i].s_part_stride = ps.s_part_stride;
+                segs[i].d_part_stride = ps.d_part_stride;
+            }
             total += ps.pp.n;
         }
         plan_strided(segs, n, strided_div64_, &splan_);
@@ -1500,11 +1569,19 @@ void NativeTransport::flush_strided()
         hipStream_t cs = copy_stream(total);
         uint64_t tiles = strided_total_tiles(splan_);
         unsigned blocks = tiles < 1024 ? (unsigned)tiles : 1024u;
-        if (strided_plan_wide(splan_))
-            hipLaunchKernelGGL(k_pull_strided<true>, dim3(blocks),
+        const bool wide = strided_plan_wide(splan_);
+        const bool parts = strided_plan_parts(splan_);
+        if (wide && parts)
+            hipLaunchKernelGGL((k_pull_strided<true, true>), dim3(blocks),
+                               dim3(PULL_THREADS), 0, cs, splan_);
+        else if (wide)
+            hipLaunchKernelGGL((k_pull_strided<true, false>), dim3(blocks),
+                               dim3(PULL_THREADS), 0, cs, splan_);
+        else if (parts)
+            hipLaunchKernelGGL((k_pull_strided<false, true>), dim3(blocks),
                                dim3(PULL_THREADS), 0, cs, splan_);
         else
-            hipLaunchKernelGGL(k_pull_strided<false>, dim3(blocks),
+            hipLaunchKernelGGL((k_pull_strided<false, false>), dim3(blocks),
                                dim3(PULL_THREADS), 0, cs, splan_);
         hipError_t e = hipGetLastError();
         if (e != hipSuccess) {
@@ -1527,8 +1604,8 @@ void NativeTransport::flush_strided()
         batches_.push_back(std::move(b));
         if (trace_on())
             fprintf(stderr, "[mpix trace] strided pull batch n=%zu tiles=%lu "
-                    "total=%lu B\n", n, (unsigned long)tiles,
-                    (unsigned long)total);
+                    "total=%lu B wide=%d parts=%d\n", n, (unsigned long)tiles,
+                    (unsigned long)total, (int)wide, (int)parts);
     }
 }
 

@@ -14,6 +14,16 @@
  * a 32-bit multiply and shift (StridedDiv); beyond that (`wide`) it uses
  * 64-bit division.  Counts and run lengths larger than the entry are clamped
  * to it, which changes no quotient and makes them fit.
+ *
+ * An entry may be a RUN of k partitions (part_run.h) of part_units granules
+ * each, part strides apart on each side.  Partitions have the same size on
+ * both sides, so the split q = u / part_units, u' = u - q * part_units is
+ * shared: one more division per unit, then per side
+ *     offset = q * part_stride + (the walk above on u')
+ * which is part_layout_offset(l, part_stride, u * granule).  Runs and counts
+ * are then clamped to part_units.  An entry without a partition level has
+ * part_units == units (q is always 0); the kernel variant that carries the
+ * third division is launched only when a batch holds a run entry.
  */
 #ifndef MPIX_TRANSPORT_STRIDED_PLAN_H
 #define MPIX_TRANSPORT_STRIDED_PLAN_H
@@ -76,25 +86,38 @@ struct StridedEntry {
     StridedSide d;  /* destination walk */
     uint32_t glog;  /* log2(granule): 4 = vector path, 3..0 = element path */
     uint32_t wide;  /* units >= 2^31: 64-bit division in the kernel */
+    /* partition level: units == k * part_units; part_units == units (and the
+     * part strides 0) when the entry is one message */
+    uint64_t part_units;
+    StridedDiv d_part; /* valid when !wide */
+    int64_t s_part_stride; /* bytes between partitions at the source */
+    int64_t d_part_stride; /* ... at the destination */
 };
 
-/* Passed BY VALUE as the kernel argument (2184 bytes). */
+/* Passed BY VALUE as the kernel argument (2696 bytes). */
 struct StridedTable {
     uint32_t n;
     uint32_t _pad;
     uint64_t tile_end[MPIX_STRIDED_BATCH]; /* tiles in entries 0..i */
     StridedEntry e[MPIX_STRIDED_BATCH];
 };
+static_assert(sizeof(StridedTable) <= 4096,
+              "StridedTable travels as the kernel argument (4096-byte limit)");
 
 /* one ready strided pull, as collected by the transport: the first `bytes`
  * message bytes go from `src` (laid out as sl) to `dst` (laid out as dl);
- * both layouts normalised, bytes > 0 and a multiple of `granule` */
+ * both layouts normalised, bytes > 0 and a multiple of `granule`.
+ * parts > 1: a run of that many whole partitions, each laid out as sl / dl,
+ * s_part_stride / d_part_stride bytes apart; `bytes` is all of them. */
 struct StridedSeg {
     void *dst;
     const void *src;
     uint64_t bytes;
     MPIX_Layout sl;
     MPIX_Layout dl;
+    uint32_t parts = 1;
+    int64_t s_part_stride = 0;
+    int64_t d_part_stride = 0;
 };
 
 static inline uint64_t strided_total_tiles(const StridedTable &t)
@@ -125,6 +148,40 @@ static inline int64_t strided_side_offset(const StridedSide &s, uint64_t u,
     }
     return (int64_t)p * s.stride1 + (int64_t)rr * s.stride0 +
            (int64_t)(o << glog);
+}
+
+/* does the entry have a partition level? */
+#if defined(__HIPCC__)
+__host__ __device__
+#endif
+static inline bool strided_entry_parts(const StridedEntry &e)
+{
+    return e.part_units < e.units;
+}
+
+/* source and destination offsets of unit u of an entry: what the kernel
+ * computes.  `parts` false skips the partition split (right only for
+ * entries without a partition level). */
+#if defined(__HIPCC__)
+__host__ __device__
+#endif
+static inline void strided_entry_offsets(const StridedEntry &e, uint64_t u,
+                                         bool wide, bool parts,
+                                         int64_t *soff, int64_t *doff)
+{
+    int64_t sb = 0, db = 0;
+    if (parts) {
+        uint64_t q;
+        if (wide)
+            q = u / e.part_units;
+        else
+            q = strided_div((uint32_t)u, e.d_part);
+        u -= q * e.part_units;
+        sb = (int64_t)q * e.s_part_stride;
+        db = (int64_t)q * e.d_part_stride;
+    }
+    *soff = sb + strided_side_offset(e.s, u, e.glog, wide);
+    *doff = db + strided_side_offset(e.d, u, e.glog, wide);
 }
 
 static inline void strided_side_prepare(const MPIX_Layout &l, uint64_t units,
@@ -162,8 +219,11 @@ static inline size_t plan_strided(const StridedSeg *in, size_t n,
     uint64_t tiles = 0;
     for (size_t i = 0; i < n; i++) {
         StridedEntry &e = out->e[i];
+        const bool parts = in[i].parts > 1;
         uint32_t g = layout_granule(in[i].sl, (uint64_t)(uintptr_t)in[i].src,
-                                    in[i].dl, (uint64_t)(uintptr_t)in[i].dst);
+                                    in[i].dl, (uint64_t)(uintptr_t)in[i].dst,
+                                    parts ? in[i].s_part_stride : 0,
+                                    parts ? in[i].d_part_stride : 0);
         uint32_t glog = 0;
         while ((1u << glog) < g) glog++;
         e.dst = (char *)in[i].dst;
@@ -171,8 +231,13 @@ static inline size_t plan_strided(const StridedSeg *in, size_t n,
         e.units = in[i].bytes >> glog;
         e.glog = glog;
         e.wide = (force_wide || e.units >= ((uint64_t)1 << 31)) ? 1 : 0;
-        strided_side_prepare(in[i].sl, e.units, glog, e.wide != 0, &e.s);
-        strided_side_prepare(in[i].dl, e.units, glog, e.wide != 0, &e.d);
+        e.part_units = parts ? e.units / in[i].parts : e.units;
+        e.s_part_stride = parts ? in[i].s_part_stride : 0;
+        e.d_part_stride = parts ? in[i].d_part_stride : 0;
+        e.d_part = StridedDiv{0, 0};
+        if (!e.wide) e.d_part = strided_div_prepare((uint32_t)e.part_units);
+        strided_side_prepare(in[i].sl, e.part_units, glog, e.wide != 0, &e.s);
+        strided_side_prepare(in[i].dl, e.part_units, glog, e.wide != 0, &e.d);
         uint64_t b = in[i].bytes;
         tiles += b / MPIX_STRIDED_TILE + (b % MPIX_STRIDED_TILE != 0);
         out->tile_end[i] = tiles;
@@ -180,6 +245,14 @@ static inline size_t plan_strided(const StridedSeg *in, size_t n,
     out->n = (uint32_t)n;
     out->_pad = 0;
     return n;
+}
+
+/* does this launch need the kernel with the partition level? */
+static inline bool strided_plan_parts(const StridedTable &t)
+{
+    for (uint32_t i = 0; i < t.n; i++)
+        if (strided_entry_parts(t.e[i])) return true;
+    return false;
 }
 
 /* does this launch need the 64-bit-division kernel? */
