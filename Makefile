@@ -40,7 +40,8 @@ $(PYEXT): mpix/_core.o $(OBJS)
 	$(HIPCC) $(CXXFLAGS) -c $< -o $@
 
 src/transport/native.o: src/transport/pull_plan.h src/transport/layout.h \
-                        src/transport/strided_plan.h src/transport/part_run.h
+                        src/transport/strided_plan.h src/transport/part_run.h \
+                        src/transport/done_ring.h
 src/enqueue.o src/partitioned.o: src/transport/layout.h
 
 $(LIB): $(OBJS)

@@ -883,6 +883,7 @@ static int host_wait_partitioned(Request *req, MPI_Status *status)
         }
     }
     /* all partitions completed: reset for the next MPIX_Start */
+    const uint64_t t_seen = s->stats ? now_ns() : 0;
     for (int p = 0; p < req->n_partitions; p++) {
         int idx = req->part_idx[p];
         s->ops[idx].ch_done.store(0, std::memory_order_relaxed);
@@ -890,6 +891,13 @@ static int host_wait_partitioned(Request *req, MPI_Status *status)
         flag_store(idx, MPIX_FLAG_RESERVED);
     }
     req->active = false;
+    if (t_seen) {
+        const uint64_t d = now_ns() - t_seen;
+        s->reset_ns.fetch_add(d, std::memory_order_relaxed);
+        s->reset_n.fetch_add(1, std::memory_order_relaxed);
+        if (d > s->reset_max_ns.load(std::memory_order_relaxed))
+            s->reset_max_ns.store(d, std::memory_order_relaxed);
+    }
 #if MPIX_HAVE_MPI_PARTITIONED
     if (req->mpi_part_native) {
         /* reference semantics (sendrecv.cu:627): the host wait completes the

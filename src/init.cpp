@@ -11,6 +11,8 @@
  */
 #include <hip/hip_runtime.h>
 
+#include <algorithm>
+
 #include <chrono>
 
 #include "internal.h"
@@ -482,6 +484,7 @@ extern "C" int MPIX_Init(void)
     s->armed.init(4 * s->nflags);
     s->spin_before_yield = env_int("MPIX_PROXY_SPIN", 2000);
     s->stats = env_int("MPIX_STATS", 0) != 0;
+    s->settle = env_int("MPIX_SETTLE", 1) != 0;
 
     {
         std::lock_guard<std::mutex> lg(lifecycle_mutex());
@@ -674,6 +677,62 @@ extern "C" int MPIX_Finalize(void)
                     (double)s->bleg_kernel_ns / k,
                     s->bleg_done_n ? (double)s->bleg_done_ns / 1e3 /
                                          (double)s->bleg_done_n : 0.0);
+        }
+        if (s->bleg_send_done_n)
+            fprintf(stderr,
+                    "[mpix stats r%d] pull-batch send side (loopback), mean us "
+                    "over %lu batches: event->last-send-completed %.1f\n",
+                    s->world_rank, (unsigned long)s->bleg_send_done_n,
+                    (double)s->bleg_send_done_ns / 1e3 /
+                        (double)s->bleg_send_done_n);
+        if (!s->bleg_whole_ns.empty()) {
+            std::vector<uint32_t> &v = s->bleg_whole_ns;
+            std::sort(v.begin(), v.end());
+            uint64_t sum = 0;
+            for (uint32_t x : v) sum += x;
+            fprintf(stderr,
+                    "[mpix stats r%d] whole-request batches (%lu): "
+                    "launch->event us median %.1f, mean %.1f, min %.1f, "
+                    "max %.1f\n", s->world_rank, (unsigned long)v.size(),
+                    (double)v[v.size() / 2] / 1e3,
+                    (double)sum / 1e3 / (double)v.size(),
+                    (double)v.front() / 1e3, (double)v.back() / 1e3);
+        }
+        if (s->arrive_n)
+            fprintf(stderr,
+                    "[mpix stats r%d] partitioned send flags over %lu "
+                    "iterations: first->last seen PENDING us mean %.2f, max "
+                    "%.2f; walks mean %.2f, max %lu (settle %s)\n",
+                    s->world_rank, (unsigned long)s->arrive_n,
+                    (double)s->arrive_ns / 1e3 / (double)s->arrive_n,
+                    (double)s->arrive_max_ns / 1e3,
+                    (double)s->arrive_walks / (double)s->arrive_n,
+                    (unsigned long)s->arrive_walks_max,
+                    s->settle ? "on" : "off");
+        if (s->word_event_n)
+            fprintf(stderr,
+                    "[mpix stats r%d] MPIX_PULL_DONE=word: completion word "
+                    "seen -> event seen, mean us over %lu batches: %.1f\n",
+                    s->world_rank, (unsigned long)s->word_event_n,
+                    (double)s->word_event_ns / 1e3 / (double)s->word_event_n);
+        if (s->compl_groups)
+            fprintf(stderr,
+                    "[mpix stats r%d] completion groups: %lu for %lu ops "
+                    "(%.1f ops per mutex acquisition)\n", s->world_rank,
+                    (unsigned long)s->compl_groups,
+                    (unsigned long)s->compl_group_ops,
+                    (double)s->compl_group_ops / (double)s->compl_groups);
+        {
+            const uint64_t sn = s->start_n.load(), rn = s->reset_n.load();
+            fprintf(stderr,
+                    "[mpix stats r%d] main thread: arm pushes %lu; MPIX_Start "
+                    "x%lu mean %.2f us, max %.2f; partitioned wait reset loop "
+                    "x%lu mean %.2f us, max %.2f\n", s->world_rank,
+                    (unsigned long)s->arm_pushes.load(), (unsigned long)sn,
+                    sn ? (double)s->start_ns.load() / 1e3 / (double)sn : 0.0,
+                    (double)s->start_max_ns.load() / 1e3, (unsigned long)rn,
+                    rn ? (double)s->reset_ns.load() / 1e3 / (double)rn : 0.0,
+                    (double)s->reset_max_ns.load() / 1e3);
         }
     }
 

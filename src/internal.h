@@ -120,8 +120,9 @@ enum class OpKind : int32_t { NONE = 0, ISEND, IRECV, PSEND_PART, PRECV_PART };
  * (proxy thread only). */
 struct BatchStat {
     uint64_t t_ev_ns; /* batch event seen complete */
-    int left;         /* ops of the batch not yet COMPLETED */
+    int left;         /* receive ops of the batch not yet COMPLETED */
     bool first;       /* the first batch of the process (see bleg_first_*) */
+    int left_send = 0; /* loopback: its send ops not yet COMPLETED */
 };
 
 /* One in-flight operation, bound 1:1 to a flag slot. */
@@ -165,6 +166,19 @@ struct Op {
      * pre-checks it outside the completion mutex (decisions that free the
      * slot are still made under the mutex). */
     std::atomic<bool> orphaned{false};
+    /* "In the proxy's watch list, or on its way there through the armed
+     * ring."  Set by slot_arm before the push, cleared by reset(), that is
+     * by slot_free BEFORE its release store of AVAILABLE.  The proxy stops
+     * watching a slot only after it was freed (every drop in proxy.cpp
+     * follows a slot_free, its own or a host wait's), so while the flag
+     * reads true to the thread that owns the slot, the slot is walked in
+     * every pass and MPIX_Start may skip the arm: its flag_store(PENDING)
+     * (release) is met by the walk's flag_load (acquire) like any other.
+     * The next owner takes the slot with an acquire CAS on AVAILABLE, so it
+     * reads false and arms again.  A true flag is never stale; a false one
+     * may be (the proxy has not dropped the slot yet), which costs one
+     * push that the proxy dedups. */
+    std::atomic<bool> watched{false};
 
     void reset() {
         kind = OpKind::NONE; buf = nullptr; bytes = 0; count = 0;
@@ -179,6 +193,7 @@ struct Op {
         fast = false; waiter_owns_req = false;
         enq_status_target = nullptr; status_saved = false;
         orphaned.store(false, std::memory_order_relaxed);
+        watched.store(false, std::memory_order_relaxed);
     }
 };
 
@@ -223,6 +238,11 @@ struct Request {
     int count_per_part = 0;
     bool active = false;            /* between Start and Wait */
     uint32_t start_seq = 0;         /* number of MPIX_Start calls */
+    /* MPIX_STATS=1, proxy thread only: how the partitions of the current
+     * iteration of a send request were seen PENDING */
+    uint32_t st_seq = 0;            /* iteration the fields below are of */
+    uint32_t st_seen = 0, st_walks = 0;
+    uint64_t st_first_ns = 0, st_last_walk = 0;
     mpix_prequest_dev_t *dev_handle = nullptr; /* device copy (Prequest_create) */
     int32_t *dev_idx = nullptr;                /* device idx array */
     /* MPI-4.0 native partitioned passthrough (MPIX_HAVE_MPI_PARTITIONED +
@@ -369,6 +389,27 @@ struct State {
     /* runs taken on the fast path, by the pull they became: one contiguous
      * copy, one folded strided entry, one entry with a partition level */
     uint64_t run_copy = 0, run_folded = 0, run_parts = 0;
+    /* event -> last SEND op of a loopback batch COMPLETED (the sends are
+     * completed by the same walk, behind the receives) */
+    uint64_t bleg_send_done_ns = 0, bleg_send_done_n = 0;
+    /* launch -> event of the batches that carried one whole request */
+    std::vector<uint32_t> bleg_whole_ns;
+    /* partitioned send requests, per iteration: first -> last partition
+     * seen PENDING, and the walks that took (proxy thread only) */
+    uint64_t arrive_n = 0, arrive_ns = 0, arrive_max_ns = 0;
+    uint64_t arrive_walks = 0, arrive_walks_max = 0;
+    /* completion groups (one mutex acquisition each) and the ops in them */
+    uint64_t compl_groups = 0, compl_group_ops = 0;
+    /* main-thread time, counted only with MPIX_STATS=1: inside MPIX_Start,
+     * and inside the host wait of a partitioned request after its last
+     * flag was seen (the reset loop); pushes into the armed ring */
+    std::atomic<uint64_t> start_ns{0}, start_max_ns{0}, start_n{0};
+    std::atomic<uint64_t> reset_ns{0}, reset_max_ns{0}, reset_n{0};
+    std::atomic<uint64_t> arm_pushes{0};
+    /* MPIX_PULL_DONE=word: batches whose word was seen, and for them the
+     * time until the event recorded behind the same kernel was seen too */
+    uint64_t word_event_ns = 0, word_event_n = 0;
+    bool settle = true;             /* MPIX_SETTLE, see proxy.cpp */
     bool bleg_first_seen = false;
     uint64_t bleg_first_wait_ns = 0, bleg_first_call_ns = 0;
     uint64_t bleg_first_rec_ns = 0, bleg_first_kernel_ns = 0;

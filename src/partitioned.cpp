@@ -237,6 +237,7 @@ extern "C" int MPIX_Start(MPIX_Request *reqp)
         MPIX_ERR("MPIX_Start on an active partitioned request");
         return MPI_ERR_REQUEST;
     }
+    const uint64_t t_in = s->stats ? now_ns() : 0;
     req->active = true;
     req->start_seq++;
 #if MPIX_HAVE_MPI_PARTITIONED
@@ -255,12 +256,24 @@ extern "C" int MPIX_Start(MPIX_Request *reqp)
         op->ch_done.store(0, std::memory_order_relaxed);
         op->status_saved = false;
         op->pseq = req->start_seq;
-        slot_arm(idx); /* proxy dedups repeated arms */
+        /* Armed once: the slots of a persistent request stay in the proxy's
+         * watch list, in the order of the first Start, until
+         * MPIX_Request_free.  A true flag cannot be stale (Op::watched), so
+         * the PENDING stored below, or by MPIX_Pready, is seen by the next
+         * walk without a push through the armed ring. */
+        if (!op->watched.load(std::memory_order_acquire)) slot_arm(idx);
         if (!req->is_send) {
             /* post the partition's receive via the proxy */
             flag_store(idx, MPIX_FLAG_PENDING);
         }
         /* send partitions stay RESERVED until MPIX_Pready */
+    }
+    if (t_in) {
+        const uint64_t d = now_ns() - t_in;
+        s->start_ns.fetch_add(d, std::memory_order_relaxed);
+        s->start_n.fetch_add(1, std::memory_order_relaxed);
+        if (d > s->start_max_ns.load(std::memory_order_relaxed))
+            s->start_max_ns.store(d, std::memory_order_relaxed);
     }
     return MPI_SUCCESS;
 }

@@ -32,17 +32,17 @@ static inline Transport *route(Op *op)
 
 /* Transition ISSUED -> COMPLETED: save/deliver status under the completion
  * mutex (closes the proxy-vs-Wait race the reference handles with
- * mpiacx_op_completion_mutex + try_complete_wait_op, sendrecv.cu:82-104). */
-static bool complete_op(int idx, Op *op)
+ * mpiacx_op_completion_mutex + try_complete_wait_op, sendrecv.cu:82-104).
+ * The CALLER holds s->completion_mutex and counts the op into
+ * ops_completed: the walk takes the mutex once for a group of consecutive
+ * slots that complete in the same pass (see proxy_main). */
+static bool complete_op_locked(int idx, Op *op)
 {
-    State *s = g_state;
-    std::lock_guard<std::mutex> lk(s->completion_mutex);
     fill_status(&op->saved_status, op->ch_status);
     op->status_saved = true;
     if (op->enq_status_target != nullptr) {
         *op->enq_status_target = op->saved_status;
     }
-    s->ops_completed.fetch_add(1, std::memory_order_relaxed);
     if (op->orphaned.load(std::memory_order_relaxed) &&
         (op->kind == OpKind::ISEND || op->kind == OpKind::IRECV)) {
         /* user already called MPIX_Request_free: nobody will wait */
@@ -65,18 +65,34 @@ static bool trace_on()
     return v != 0;
 }
 
-/* MPIX_STATS=1: `op` has just been published complete; the last op of a
- * batched pull closes the batch's event -> COMPLETED leg. */
-static void batch_stat_op_done(State *s, BatchStat *bs)
+/* MPIX_STATS=1: an op has just been published complete; the last receive op
+ * of a batched pull closes the batch's event -> COMPLETED leg, the last of
+ * its send ops (loopback: they are completed by this proxy too) the
+ * event -> last-send leg.  Whichever comes last frees the record. */
+static void batch_stat_op_done(State *s, BatchStat *bs, bool is_send)
 {
-    if (bs == nullptr || --bs->left > 0) return;
-    if (bs->first) {
-        s->bleg_first_done_ns = now_ns() - bs->t_ev_ns;
+    if (bs == nullptr) return;
+    if (is_send) {
+        if (--bs->left_send > 0) return;
+        if (!bs->first) {
+            s->bleg_send_done_ns += now_ns() - bs->t_ev_ns;
+            s->bleg_send_done_n++;
+        }
     } else {
-        s->bleg_done_ns += now_ns() - bs->t_ev_ns;
-        s->bleg_done_n++;
+        if (--bs->left > 0) return;
+        if (bs->first) {
+            s->bleg_first_done_ns = now_ns() - bs->t_ev_ns;
+        } else {
+            s->bleg_done_ns += now_ns() - bs->t_ev_ns;
+            s->bleg_done_n++;
+        }
     }
-    delete bs;
+    if (bs->left <= 0 && bs->left_send <= 0) delete bs;
+}
+
+static inline bool op_is_send(const Op *op)
+{
+    return op->kind == OpKind::ISEND || op->kind == OpKind::PSEND_PART;
 }
 
 #define MPIX_TRACE_EV(fmt, ...)                                         \
@@ -118,30 +134,45 @@ void proxy_main()
         dead = 0;
     };
 
-    while (true) {
-        bool did = false;
-        s->proxy_passes.fetch_add(1, std::memory_order_relaxed);
-
-        /* adopt newly armed slots */
-        int nidx;
-        while (s->armed.pop(&nidx)) {
-            if (!watched[nidx]) {
-                watched[nidx] = 1;
-                watch.push_back(nidx);
-            }
-            did = true;
+    /* Completion group: consecutive slots of the walk that are ISSUED, not
+     * fast and done are completed in ONE critical section — the ops of a
+     * batched pull all become done in the same progress() call, and taking
+     * and dropping the mutex per op was most of the event -> COMPLETED leg.
+     * The group ends at the first slot in any other condition (every other
+     * branch that needs the mutex takes it itself, so it must be free
+     * there), at the end of the walk, and after GROUP_MAX ops, so that a
+     * thread waiting for the mutex (MPIX_Request_free, a status pick-up) is
+     * let in between two groups. */
+    constexpr uint64_t GROUP_MAX = 256;
+    std::unique_lock<std::mutex> glk(s->completion_mutex, std::defer_lock);
+    uint64_t group_n = 0, group_t0 = 0;
+    auto end_group = [&] {
+        if (!glk.owns_lock()) return;
+        glk.unlock();
+        s->ops_completed.fetch_add(group_n, std::memory_order_relaxed);
+        if (s->stats) {
+            s->leg_compl_ns += now_ns() - group_t0;
+            s->compl_groups++;
+            s->compl_group_ops += group_n;
         }
+        group_n = 0;
+    };
 
-        /* drive the data plane */
-        s->t_native->progress();
-        if (s->t_mpi) s->t_mpi->progress();
-
-        /* walk active slots */
+    bool did = false;
+    uint64_t walk_id = 0;
+    /* One walk over the active slots.  Returns how many PSEND_PART ops it
+     * handed to the transport. */
+    auto walk = [&]() -> int {
+        int psend_started = 0;
+        walk_id++;
         for (size_t i = 0; i < watch.size(); i++) {
             int idx = watch[i];
             if (idx < 0) continue; /* tombstone */
             Op *op = &s->ops[idx];
             uint32_t f = flag_load(idx);
+            const bool grp = f == MPIX_FLAG_ISSUED && !op->fast &&
+                             op->ch_done.load(std::memory_order_acquire);
+            if (!grp) end_group();
             switch (f) {
             case MPIX_FLAG_AVAILABLE:
                 /* freed by a host-side wait — stop watching */
@@ -160,8 +191,36 @@ void proxy_main()
                     s->leg_trig_ns += t - op->t_enq_ns;
                     op->t_enq_ns = 0;
                 }
+                if (s->stats && op->kind == OpKind::PSEND_PART &&
+                    op->req != nullptr) {
+                    /* how this iteration's flags arrive: first -> last
+                     * partition seen PENDING, and over how many walks */
+                    Request *rq = op->req;
+                    const uint64_t t = now_ns();
+                    if (rq->st_seq != op->pseq) {
+                        rq->st_seq = op->pseq;
+                        rq->st_seen = rq->st_walks = 0;
+                        rq->st_first_ns = t;
+                        rq->st_last_walk = 0;
+                    }
+                    rq->st_seen++;
+                    if (rq->st_last_walk != walk_id) {
+                        rq->st_last_walk = walk_id;
+                        rq->st_walks++;
+                    }
+                    if ((int)rq->st_seen == rq->n_partitions) {
+                        const uint64_t d = t - rq->st_first_ns;
+                        s->arrive_n++;
+                        s->arrive_ns += d;
+                        if (d > s->arrive_max_ns) s->arrive_max_ns = d;
+                        s->arrive_walks += rq->st_walks;
+                        if (rq->st_walks > s->arrive_walks_max)
+                            s->arrive_walks_max = rq->st_walks;
+                    }
+                }
                 int rc = route(op)->start(op);
                 if (rc == 0) {
+                    if (op->kind == OpKind::PSEND_PART) psend_started++;
                     MPIX_TRACE_EV("slot %d %s peer=%d tag=%d part=%d bytes=%lu"
                                   " PENDING->ISSUED", idx, (int)op->kind == 1 ?
                                   "isend" : (int)op->kind == 2 ? "irecv" :
@@ -205,7 +264,7 @@ void proxy_main()
                     MPIX_TRACE_EV("slot %d fast complete seq=%u err=%d", idx,
                                   req->seq, op->ch_status.err);
                     seq_store(idx, req->seq);
-                    batch_stat_op_done(s, op->stat_batch);
+                    batch_stat_op_done(s, op->stat_batch, op_is_send(op));
                     if (free_req) delete req;
                     s->ops_completed.fetch_add(1, std::memory_order_relaxed);
                     slot_free(idx);
@@ -213,10 +272,14 @@ void proxy_main()
                     did = true;
                     continue;
                 }
-                if (op->ch_done.load(std::memory_order_acquire)) {
+                if (grp) {
+                    if (!glk.owns_lock()) {
+                        glk.lock();
+                        /* the one timestamp of the group */
+                        group_t0 = s->stats ? now_ns() : 0;
+                    }
                     if (s->stats && op->t_issue_ns) {
-                        uint64_t t = now_ns();
-                        uint64_t d = t - op->t_issue_ns;
+                        uint64_t d = group_t0 - op->t_issue_ns;
                         s->lat_sum_ns += d;
                         s->leg_xfer_ns += d;
                         uint64_t us = d / 1000;
@@ -227,19 +290,16 @@ void proxy_main()
                     }
                     MPIX_TRACE_EV("slot %d ISSUED->COMPLETED err=%d", idx,
                                   op->ch_status.err);
-                    uint64_t tc = s->stats ? now_ns() : 0;
                     BatchStat *bs = op->stat_batch; /* op may be recycled */
                     op->stat_batch = nullptr;
-                    if (complete_op(idx, op)) { /* orphan: slot freed */
-                        if (s->stats) s->leg_compl_ns += now_ns() - tc;
-                        batch_stat_op_done(s, bs);
-                        drop(i);
-                        did = true;
-                        continue;
-                    }
-                    if (s->stats) s->leg_compl_ns += now_ns() - tc;
-                    batch_stat_op_done(s, bs);
+                    const bool snd = op_is_send(op);
+                    const bool gone = complete_op_locked(idx, op);
+                    group_n++;
+                    batch_stat_op_done(s, bs, snd);
+                    if (gone) drop(i); /* orphan: slot freed */
                     did = true;
+                    if (group_n >= GROUP_MAX) end_group();
+                    continue;
                 }
                 break;
             case MPIX_FLAG_COMPLETED: {
@@ -275,6 +335,41 @@ void proxy_main()
                 break;
             }
         }
+        end_group();
+        return psend_started;
+    };
+
+    while (true) {
+        did = false;
+        s->proxy_passes.fetch_add(1, std::memory_order_relaxed);
+
+        /* adopt newly armed slots */
+        int nidx;
+        while (s->armed.pop(&nidx)) {
+            if (!watched[nidx]) {
+                watched[nidx] = 1;
+                watch.push_back(nidx);
+            }
+            did = true;
+        }
+
+        /* drive the data plane */
+        s->t_native->progress();
+        if (s->t_mpi) s->t_mpi->progress();
+
+        /* Walk the active slots.  Settle: the walk is where PENDING is
+         * noticed, and a kernel's Pready stores land while it is under way,
+         * so the slots behind the cursor used to wait for the next pass and
+         * became a second run: a second descriptor, launch and completion.
+         * A walk that started partitioned sends is therefore repeated at
+         * once, before progress() announces anything, until a walk starts
+         * none (4 walks at most).  The spread between the first and the
+         * last flag of a kernel-triggered request is of the order of one
+         * walk (profiles/batch_handoffs.md), which is why the rule counts
+         * walks and not time.  A producer that publishes partitions over
+         * time pays one more walk per publication, well under a
+         * microsecond; MPIX_SETTLE=0 turns it off. */
+        for (int w = 1; walk() > 0 && s->settle && w < 4; w++) {}
         compact();
 
         if (s->proxy_stop.load(std::memory_order_acquire) &&

@@ -50,7 +50,11 @@ void slot_free(int idx)
 
 void slot_arm(int idx)
 {
-    g_state->armed.push(idx);
+    State *s = g_state;
+    /* before the push: see Op::watched */
+    s->ops[idx].watched.store(true, std::memory_order_relaxed);
+    if (s->stats) s->arm_pushes.fetch_add(1, std::memory_order_relaxed);
+    s->armed.push(idx);
 }
 
 /* ------------------------------------------------------------------- utils */

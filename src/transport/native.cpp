@@ -46,6 +46,7 @@
 
 #include "../internal.h"
 #include "bootstrap.h"
+#include "done_ring.h"
 #include "layout.h"
 #include "part_run.h"
 #include "pull_plan.h"
@@ -67,9 +68,12 @@ namespace mpix {
  * payload is touched once, and keeping it out of the caches is what
  * measured faster than the one-vector-per-thread kernel this replaces
  * (profiles/pull_stream_copy.md).  The partial last tile of a copy
- * and its n % 16 tail bytes take the slow branch.  No spin-wait and no
- * completion signal in here: completion stays the event recorded behind
- * the launch (see maybe_switch_prio for why nothing may park on a queue). */
+ * and its n % 16 tail bytes take the slow branch.  No spin-wait in here, in
+ * either variant (see maybe_switch_prio for why nothing may park on a
+ * queue).  k_pull_multi carries no completion signal: its completion is the
+ * event recorded behind the launch.  k_pull_multi_done (MPIX_PULL_DONE=word)
+ * is the same copy followed by pull_signal_done, which nothing waits for
+ * on the device either. */
 #define PULL_THREADS 256
 typedef unsigned int pull_v4 __attribute__((ext_vector_type(4)));
 typedef const __attribute__((address_space(1))) pull_v4 *pull_gsrc;
@@ -90,8 +94,46 @@ static __device__ __forceinline__ void pull_st(pull_gdst p, pull_v4 v)
         *p = v;
 }
 
+/* Completion word (done_ring.h), device side.  Every block arrives at the
+ * slot's counter once its own stores are out of the XCD's L2; the block
+ * whose add is the last of the grid zeroes the counter for the slot's next
+ * user and publishes the sequence number to the host word.  Nothing waits
+ * and nothing spins.
+ *  - each wave drains its own stores (vmcnt counts stores on gfx9), then the
+ *    block barrier: thread 0 signals for all waves of the block;
+ *  - agent-scope release before the add: nontemporal stores stay in the L2
+ *    of the XCD, and the host word must not overtake them.  The wait behind
+ *    the fence is written as asm so that it cannot be dropped;
+ *  - the last arriver's add returned gridDim.x - 1, so every other block's
+ *    release happened before it; its system-scope release store orders the
+ *    counter reset and the word behind all of that. */
+struct PullDone {
+    uint32_t *counter; /* device memory, 0 between uses */
+    uint64_t *word;    /* pinned host memory */
+    uint64_t seq;
+};
+
+static __device__ __forceinline__ void pull_signal_done(const PullDone &d)
+{
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        const uint32_t before = __hip_atomic_fetch_add(
+            d.counter, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        if (before == gridDim.x - 1) {
+            __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
+            __hip_atomic_store(d.counter, 0u, __ATOMIC_RELAXED,
+                               __HIP_MEMORY_SCOPE_AGENT);
+            __hip_atomic_store(d.word, d.seq, __ATOMIC_RELEASE,
+                               __HIP_MEMORY_SCOPE_SYSTEM);
+        }
+    }
+}
+
 template <int U, bool NT>
-__global__ __launch_bounds__(PULL_THREADS) void k_pull_multi(const PullTable t)
+static __device__ __forceinline__ void pull_multi_body(const PullTable &t)
 {
     constexpr uint64_t TILE = (uint64_t)PULL_THREADS * U * 16;
     const uint64_t total = t.tile_end[t.ncopies - 1];
@@ -131,6 +173,20 @@ __global__ __launch_bounds__(PULL_THREADS) void k_pull_multi(const PullTable t)
             }
         }
     }
+}
+
+template <int U, bool NT>
+__global__ __launch_bounds__(PULL_THREADS) void k_pull_multi(const PullTable t)
+{
+    pull_multi_body<U, NT>(t);
+}
+
+template <int U, bool NT>
+__global__ __launch_bounds__(PULL_THREADS) void k_pull_multi_done(
+    const PullTable t, const PullDone d)
+{
+    pull_multi_body<U, NT>(t);
+    pull_signal_done(d);
 }
 
 /* Strided pull: the same launch shape for messages that are strided on
@@ -188,8 +244,7 @@ static __device__ __forceinline__ void strided_tile(const StridedEntry &e,
 }
 
 template <bool WIDE, bool PARTS>
-__global__ __launch_bounds__(PULL_THREADS) void k_pull_strided(
-    const StridedTable t)
+static __device__ __forceinline__ void pull_strided_body(const StridedTable &t)
 {
     const uint64_t total = t.tile_end[t.n - 1];
     uint32_t c = 0;
@@ -213,6 +268,22 @@ __global__ __launch_bounds__(PULL_THREADS) void k_pull_strided(
         default: strided_tile<uint8_t, 16, WIDE, PARTS>(cur, unit0); break;
         }
     }
+}
+
+template <bool WIDE, bool PARTS>
+__global__ __launch_bounds__(PULL_THREADS) void k_pull_strided(
+    const StridedTable t)
+{
+    pull_strided_body<WIDE, PARTS>(t);
+}
+
+/* MPIX_PULL_DONE=word: see pull_signal_done */
+template <bool WIDE, bool PARTS>
+__global__ __launch_bounds__(PULL_THREADS) void k_pull_strided_done(
+    const StridedTable t, const PullDone d)
+{
+    pull_strided_body<WIDE, PARTS>(t);
+    pull_signal_done(d);
 }
 
 /* Sender-push threshold for small DEVICE payloads: stage D2H into the shm
@@ -251,6 +322,23 @@ static bool part_runs_on()
     static const bool v = [] {
         const char *e = getenv("MPIX_PART_RUNS");
         return e ? atoi(e) != 0 : true;
+    }();
+    return v;
+}
+
+/* MPIX_PULL_DONE=word|event, read once: how a pull kernel's completion
+ * reaches the proxy.  event (default): an event recorded behind the launch
+ * and tested with hipEventQuery in every pass.  word: the kernel's last
+ * block stores a sequence number to pinned host memory (done_ring.h,
+ * pull_signal_done); no event, no runtime call per pass.  The A/B is in
+ * profiles/batch_handoffs.md. */
+static bool pull_done_word()
+{
+    static const bool v = [] {
+        const char *e = getenv("MPIX_PULL_DONE");
+        if (e != nullptr && strcmp(e, "word") != 0 && strcmp(e, "event") != 0)
+            MPIX_ERR("MPIX_PULL_DONE=%s is neither word nor event: event", e);
+        return e != nullptr && strcmp(e, "word") == 0;
     }();
     return v;
 }
@@ -449,14 +537,40 @@ private:
     void finish_pull(const PendingPull &pp, BatchStat *bs);
     std::vector<PendingPull> pend_pulls_;
     struct PullBatch {
-        hipEvent_t ev;
-        uint64_t t_launch_ns; /* MPIX_STATS=1 */
-        bool first;           /* MPIX_STATS=1: first batch of the process */
+        hipEvent_t ev = nullptr; /* event path; word path: only MPIX_STATS=1 */
+        int done_slot = -1;   /* word path: slot of done_ring_, else -1 */
+        hipStream_t cs = nullptr;
+        uint64_t t_born_ns = 0;  /* word path: for the lost-signal guard */
+        uint32_t passes = 0;     /* word path: passes that found no word */
+        uint64_t t_launch_ns = 0; /* MPIX_STATS=1 */
+        bool first = false;   /* MPIX_STATS=1: first batch of the process */
         std::vector<PendingPull> items;
     };
     std::list<PullBatch> batches_;
+    /* MPIX_PULL_DONE=word: completion words in pinned host memory, one per
+     * 64 bytes, and arrival counters in device memory, one per 128 bytes
+     * (done_ring.h has the bookkeeping) */
+    static constexpr size_t DONE_WORD_STRIDE = 8;     /* in uint64_t */
+    static constexpr size_t DONE_COUNTER_STRIDE = 32; /* in uint32_t */
+    bool done_word_ = false;
+    DoneRing done_ring_;
+    std::atomic<uint64_t> *done_words_ = nullptr; /* host view */
+    uint64_t *done_words_d_ = nullptr;            /* device view */
+    uint32_t *done_counters_ = nullptr;
+    /* a batch on the word path: slot and kernel argument, or -1 (event
+     * path: MPIX_PULL_DONE=event, or the ring is full) */
+    int done_begin(PullDone *d);
+    /* MPIX_STATS=1 with word: the event recorded all the same, kept after
+     * the word was seen to measure word seen -> event seen */
+    struct WordEvent {
+        hipEvent_t ev;
+        uint64_t t_word_ns;
+    };
+    std::list<WordEvent> word_events_;
+    bool batch_done(PullBatch &b, hipError_t *err);
+    void close_batch(PullBatch &b, hipStream_t cs, int slot, bool stats);
     PullTable plan_{}; /* scratch of flush_pulls; passed by value */
-    void launch_pull(unsigned blocks, hipStream_t cs);
+    void launch_pull(unsigned blocks, hipStream_t cs, const PullDone *done);
 
     /* strided pulls collected this progress pass: ONE k_pull_strided launch
      * per MPIX_STRIDED_BATCH of them, completed through batches_ like the
@@ -699,6 +813,25 @@ int NativeTransport::init()
          * 36.5 to ~55 us.  Batched pulls serialize on stream 0 at HBM
          * rate, so extra streams buy nothing; MPIX_COPY_PRIO_STREAM=1
          * opts a standing priority stream back in for experiments. */
+        if (pull_done_word()) {
+            void *w = nullptr, *wd = nullptr, *c = nullptr;
+            const size_t wbytes =
+                MPIX_DONE_SLOTS * DONE_WORD_STRIDE * sizeof(uint64_t);
+            const size_t cbytes =
+                MPIX_DONE_SLOTS * DONE_COUNTER_STRIDE * sizeof(uint32_t);
+            if (hipHostMalloc(&w, wbytes, hipHostMallocMapped) != hipSuccess ||
+                hipHostGetDevicePointer(&wd, w, 0) != hipSuccess ||
+                hipMalloc(&c, cbytes) != hipSuccess ||
+                hipMemset(c, 0, cbytes) != hipSuccess) {
+                MPIX_ERR("MPIX_PULL_DONE=word: completion words not allocated");
+                return -1;
+            }
+            memset(w, 0, wbytes);
+            done_words_ = reinterpret_cast<std::atomic<uint64_t> *>(w);
+            done_words_d_ = (uint64_t *)wd;
+            done_counters_ = (uint32_t *)c;
+            done_word_ = true;
+        }
         if (env_flag("MPIX_COPY_PRIO_STREAM")) {
             int lo = 0, hi = 0;
             if (hipDeviceGetStreamPriorityRange(&lo, &hi) == hipSuccess &&
@@ -725,8 +858,16 @@ void NativeTransport::shutdown()
     if (boot_) boot_->barrier();
     for (auto &kv : ipc_open_) (void)hipIpcCloseMemHandle(kv.second);
     ipc_open_.clear();
+    for (WordEvent &we : word_events_) event_pool_.push_back(we.ev);
+    word_events_.clear();
     for (hipEvent_t ev : event_pool_) (void)hipEventDestroy(ev);
     event_pool_.clear();
+    if (done_words_) (void)hipHostFree((void *)done_words_);
+    if (done_counters_) (void)hipFree(done_counters_);
+    done_words_ = nullptr;
+    done_words_d_ = nullptr;
+    done_counters_ = nullptr;
+    done_word_ = false;
     for (int i = 0; i < N_COPY_STREAMS; i++) {
         if (copy_streams_[i]) (void)hipStreamDestroy(copy_streams_[i]);
         copy_streams_[i] = nullptr;
@@ -1193,6 +1334,22 @@ bool NativeTransport::try_run_fast_path(int src, const Desc &d, uint32_t k)
  * flag transitions stay with the proxy walk); the sender gets ONE ack. */
 void NativeTransport::finish_pull(const PendingPull &pp, BatchStat *bs)
 {
+    if (bs != nullptr && pp.src == rank_) {
+        /* MPIX_STATS=1, loopback: the send ops this ack completes belong to
+         * the batch's event -> last-send leg (before the ack: it erases the
+         * entry) */
+        auto it = await_done_.find(pp.token);
+        if (it != await_done_.end()) {
+            const AwaitDone &a = it->second;
+            for (uint32_t j = 0; j < pp.k; j++) {
+                Op *so = a.run.k == 1
+                    ? a.op
+                    : &g_state->ops[a.req->part_idx[pp.partition + (int32_t)j]];
+                so->stat_batch = bs;
+                bs->left_send++;
+            }
+        }
+    }
     ack(pp.src, pp.token, pp.partition, pp.k);
     for (uint32_t j = 0; j < pp.k; j++) {
         Op *op = pull_op(pp, j);
@@ -1451,8 +1608,17 @@ static bool pull_nontemporal()
 
 template <int U>
 static void launch_pull_u(bool nt, unsigned blocks, hipStream_t cs,
-                          const PullTable &t)
+                          const PullTable &t, const PullDone *done)
 {
+    if (done != nullptr) {
+        if (nt)
+            hipLaunchKernelGGL((k_pull_multi_done<U, true>), dim3(blocks),
+                               dim3(PULL_THREADS), 0, cs, t, *done);
+        else
+            hipLaunchKernelGGL((k_pull_multi_done<U, false>), dim3(blocks),
+                               dim3(PULL_THREADS), 0, cs, t, *done);
+        return;
+    }
     if (nt)
         hipLaunchKernelGGL((k_pull_multi<U, true>), dim3(blocks),
                            dim3(PULL_THREADS), 0, cs, t);
@@ -1461,13 +1627,40 @@ static void launch_pull_u(bool nt, unsigned blocks, hipStream_t cs,
                            dim3(PULL_THREADS), 0, cs, t);
 }
 
-void NativeTransport::launch_pull(unsigned blocks, hipStream_t cs)
+void NativeTransport::launch_pull(unsigned blocks, hipStream_t cs,
+                                  const PullDone *done)
 {
     const bool nt = pull_nontemporal();
     switch (pull_unroll()) {
-    case 1: launch_pull_u<1>(nt, blocks, cs, plan_); break;
-    case 8: launch_pull_u<8>(nt, blocks, cs, plan_); break;
-    default: launch_pull_u<4>(nt, blocks, cs, plan_); break;
+    case 1: launch_pull_u<1>(nt, blocks, cs, plan_, done); break;
+    case 8: launch_pull_u<8>(nt, blocks, cs, plan_, done); break;
+    default: launch_pull_u<4>(nt, blocks, cs, plan_, done); break;
+    }
+}
+
+int NativeTransport::done_begin(PullDone *d)
+{
+    if (!done_word_) return -1;
+    uint64_t seq = 0;
+    const int slot = done_acquire(&done_ring_, &seq);
+    if (slot < 0) return -1; /* ring full: this batch takes the event path */
+    d->counter = done_counters_ + (size_t)slot * DONE_COUNTER_STRIDE;
+    d->word = done_words_d_ + (size_t)slot * DONE_WORD_STRIDE;
+    d->seq = seq;
+    return slot;
+}
+
+/* What follows a successful launch: the word path records no event (with
+ * MPIX_STATS=1 it does, to measure what the event would have cost). */
+void NativeTransport::close_batch(PullBatch &b, hipStream_t cs, int slot,
+                                  bool stats)
+{
+    b.done_slot = slot;
+    b.cs = cs;
+    if (slot >= 0) b.t_born_ns = now_ns();
+    if (slot < 0 || stats) {
+        b.ev = get_event();
+        (void)hipEventRecord(b.ev, cs);
     }
 }
 
@@ -1496,12 +1689,15 @@ void NativeTransport::flush_pulls()
         }();
         uint64_t tiles = pull_total_tiles(plan_);
         unsigned blocks = tiles < max_blocks ? (unsigned)tiles : max_blocks;
+        PullDone done;
+        const int slot = done_begin(&done);
         const uint64_t t_call = stats ? now_ns() : 0;
-        launch_pull(blocks, cs);
+        launch_pull(blocks, cs, slot >= 0 ? &done : nullptr);
         hipError_t e = hipGetLastError();
         const uint64_t t_rec = stats ? now_ns() : 0;
         if (e != hipSuccess) {
             MPIX_ERR("k_pull_multi launch failed: %s", hipGetErrorString(e));
+            if (slot >= 0) done_release(&done_ring_, slot);
             for (size_t i = 0; i < n; i++) {
                 pend_pulls_[i].st.err = MPI_ERR_OTHER;
                 finish_pull(pend_pulls_[i], nullptr);
@@ -1510,10 +1706,7 @@ void NativeTransport::flush_pulls()
             continue;
         }
         PullBatch b;
-        b.ev = get_event();
-        (void)hipEventRecord(b.ev, cs);
-        b.t_launch_ns = 0;
-        b.first = false;
+        close_batch(b, cs, slot, stats);
         if (stats) {
             State *s = g_state;
             b.t_launch_ns = now_ns();
@@ -1571,21 +1764,30 @@ void NativeTransport::flush_strided()
         unsigned blocks = tiles < 1024 ? (unsigned)tiles : 1024u;
         const bool wide = strided_plan_wide(splan_);
         const bool parts = strided_plan_parts(splan_);
+        PullDone done;
+        const int slot = done_begin(&done);
+#define MPIX_LAUNCH_STRIDED(W, P)                                            \
+        do {                                                                  \
+            if (slot >= 0)                                                    \
+                hipLaunchKernelGGL((k_pull_strided_done<W, P>), dim3(blocks), \
+                                   dim3(PULL_THREADS), 0, cs, splan_, done);  \
+            else                                                              \
+                hipLaunchKernelGGL((k_pull_strided<W, P>), dim3(blocks),      \
+                                   dim3(PULL_THREADS), 0, cs, splan_);        \
+        } while (0)
         if (wide && parts)
-            hipLaunchKernelGGL((k_pull_strided<true, true>), dim3(blocks),
-                               dim3(PULL_THREADS), 0, cs, splan_);
+            MPIX_LAUNCH_STRIDED(true, true);
         else if (wide)
-            hipLaunchKernelGGL((k_pull_strided<true, false>), dim3(blocks),
-                               dim3(PULL_THREADS), 0, cs, splan_);
+            MPIX_LAUNCH_STRIDED(true, false);
         else if (parts)
-            hipLaunchKernelGGL((k_pull_strided<false, true>), dim3(blocks),
-                               dim3(PULL_THREADS), 0, cs, splan_);
+            MPIX_LAUNCH_STRIDED(false, true);
         else
-            hipLaunchKernelGGL((k_pull_strided<false, false>), dim3(blocks),
-                               dim3(PULL_THREADS), 0, cs, splan_);
+            MPIX_LAUNCH_STRIDED(false, false);
+#undef MPIX_LAUNCH_STRIDED
         hipError_t e = hipGetLastError();
         if (e != hipSuccess) {
             MPIX_ERR("k_pull_strided launch failed: %s", hipGetErrorString(e));
+            if (slot >= 0) done_release(&done_ring_, slot);
             for (size_t i = 0; i < n; i++) {
                 pend_strided_[i].pp.st.err = MPI_ERR_OTHER;
                 finish_pull(pend_strided_[i].pp, nullptr);
@@ -1594,11 +1796,9 @@ void NativeTransport::flush_strided()
                                 pend_strided_.begin() + n);
             continue;
         }
-        PullBatch b;
-        b.ev = get_event();
-        (void)hipEventRecord(b.ev, cs);
-        b.t_launch_ns = 0; /* the batch legs of MPIX_STATS count plain pulls */
-        b.first = false;
+        PullBatch b; /* t_launch_ns stays 0: the batch legs of MPIX_STATS
+                        count plain pulls */
+        close_batch(b, cs, slot, g_state != nullptr && g_state->stats);
         for (size_t i = 0; i < n; i++) b.items.push_back(pend_strided_[i].pp);
         pend_strided_.erase(pend_strided_.begin(), pend_strided_.begin() + n);
         batches_.push_back(std::move(b));
@@ -1609,15 +1809,64 @@ void NativeTransport::flush_strided()
     }
 }
 
+/* Is the batch's kernel finished?  *err: hipSuccess, or why its ops fail.
+ * Event path: hipEventQuery.  Word path: a plain acquire load of the slot's
+ * host word, no runtime call.  A kernel that dies never stores its word, so
+ * for a batch older than a second the stream is asked, once per 4096 passes
+ * that found no word: an error there fails the batch (reasoned, not
+ * exercised: nothing in the tests makes a kernel fail). */
+bool NativeTransport::batch_done(PullBatch &b, hipError_t *err)
+{
+    *err = hipSuccess;
+    if (b.done_slot < 0) {
+        hipError_t e = hipEventQuery(b.ev);
+        if (e == hipErrorNotReady) return false;
+        *err = e;
+        put_event(b.ev);
+        b.ev = nullptr;
+        return true;
+    }
+    const uint64_t w =
+        done_words_[(size_t)b.done_slot * DONE_WORD_STRIDE].load(
+            std::memory_order_acquire);
+    if (!done_seen(&done_ring_, b.done_slot, w)) {
+        if ((++b.passes & 4095u) != 0 ||
+            now_ns() - b.t_born_ns < 1000000000ull)
+            return false;
+        hipError_t e = hipStreamQuery(b.cs);
+        if (e == hipSuccess || e == hipErrorNotReady) return false;
+        MPIX_ERR("pull kernel lost (no completion word after %.1f s): %s",
+                 (double)(now_ns() - b.t_born_ns) / 1e9, hipGetErrorString(e));
+        *err = e;
+    }
+    done_release(&done_ring_, b.done_slot);
+    b.done_slot = -1;
+    if (b.ev != nullptr) {
+        /* MPIX_STATS=1: how long after the word does the event follow? */
+        word_events_.push_back(WordEvent{b.ev, now_ns()});
+        b.ev = nullptr;
+    }
+    return true;
+}
+
 int NativeTransport::progress_copies()
 {
-    for (auto it = batches_.begin(); it != batches_.end();) {
-        hipError_t e = hipEventQuery(it->ev);
-        if (e == hipErrorNotReady) {
+    for (auto it = word_events_.begin(); it != word_events_.end();) {
+        if (hipEventQuery(it->ev) == hipErrorNotReady) {
             ++it;
             continue;
         }
+        g_state->word_event_ns += now_ns() - it->t_word_ns;
+        g_state->word_event_n++;
         put_event(it->ev);
+        it = word_events_.erase(it);
+    }
+    for (auto it = batches_.begin(); it != batches_.end();) {
+        hipError_t e;
+        if (!batch_done(*it, &e)) {
+            ++it;
+            continue;
+        }
         BatchStat *bs = nullptr;
         if (it->t_launch_ns) {
             bs = new BatchStat{now_ns(),
@@ -1627,6 +1876,14 @@ int NativeTransport::progress_copies()
                 g_state->bleg_first_kernel_ns = bs->t_ev_ns - it->t_launch_ns;
             else
                 g_state->bleg_kernel_ns += bs->t_ev_ns - it->t_launch_ns;
+            /* a batch that is one whole request: its launch -> event is
+             * comparable with the kernel's traced duration */
+            const PendingPull &p0 = it->items.front();
+            if (!it->first && it->items.size() == 1 && p0.k > 1 &&
+                p0.op->req != nullptr &&
+                (int)p0.k == p0.op->req->n_partitions)
+                g_state->bleg_whole_ns.push_back(
+                    (uint32_t)(bs->t_ev_ns - it->t_launch_ns));
         }
         for (PendingPull &pp : it->items) {
             if (e != hipSuccess) pp.st.err = MPI_ERR_OTHER;
