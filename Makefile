@@ -41,7 +41,8 @@ $(PYEXT): mpix/_core.o $(OBJS)
 
 src/transport/native.o: src/transport/pull_plan.h src/transport/layout.h \
                         src/transport/strided_plan.h src/transport/part_run.h \
-                        src/transport/done_ring.h
+                        src/transport/done_ring.h src/transport/pull_kernels.h \
+                        src/transport/shm_ring.h
 src/enqueue.o src/partitioned.o: src/transport/layout.h
 
 $(LIB): $(OBJS)

@@ -153,7 +153,6 @@ struct Op {
     uint64_t t_issue_ns = 0;        /* proxy-side stats (MPIX_STATS=1) */
     std::atomic<int> ch_done{0};
     ChStatus ch_status;
-    void *ch_priv = nullptr;        /* channel-private per-op state */
     BatchStat *stat_batch = nullptr; /* batched pull it rode (MPIX_STATS=1) */
 
     /* completion/status delivery (guarded by g_state->completion_mutex) */
@@ -189,7 +188,7 @@ struct Op {
         partition = -1; pseq = 0; req = nullptr;
         t_enq_ns = 0; t_issue_ns = 0;
         ch_done.store(0, std::memory_order_relaxed);
-        ch_status = ChStatus{}; ch_priv = nullptr; stat_batch = nullptr;
+        ch_status = ChStatus{}; stat_batch = nullptr;
         fast = false; waiter_owns_req = false;
         enq_status_target = nullptr; status_saved = false;
         orphaned.store(false, std::memory_order_relaxed);
@@ -327,8 +326,9 @@ struct State {
     bool use_capture_memops = false; /* memOps recordable under capture */
     /* sticky: a spin-WAIT kernel has been emitted (graph node, captured, or
      * stream fallback).  While false, no spinning kernel can exist on any
-     * HSA queue, so the transport may run its pull copy as a compute
-     * kernel; once true, copies ride SDMA (see pull_kernels_safe). */
+     * HSA queue, so the transport's copy stream is a plain one; once true,
+     * it is a greatest-priority stream, which shares a hardware queue with
+     * no user stream (maybe_switch_prio in transport/native.cpp). */
     std::atomic<bool> spin_wait_kernels{false};
     /* flag pool */
     size_t nflags = 0;

@@ -3,7 +3,7 @@
  *
  * With MPIX_PULL_DONE=word a pull kernel tells the proxy that it has finished
  * by storing a sequence number into a 64-bit word in pinned host memory (the
- * kernel side is pull_signal_done in native.cpp) instead of through an event
+ * kernel side is pull_signal_done in pull_kernels.h) instead of through an event
  * recorded behind the launch.  The words form a small ring of
  * MPIX_DONE_SLOTS; each slot also owns a 32-bit arrival counter in device
  * memory, which the kernel's last block leaves at 0 again.

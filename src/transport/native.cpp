@@ -7,10 +7,12 @@
  *
  *  control plane  per ordered rank pair (s -> r), an SPSC descriptor ring in
  *                 a POSIX shm segment owned by r, plus a chunked staging
- *                 buffer for host payloads.
+ *                 buffer for host payloads (shm_ring.h).
  *  device data    sender publishes {hipIpcMemHandle, offset}; the RECEIVER
- *                 pulls with hipMemcpyAsync over xGMI (SDMA) on a private
- *                 stream and acks with a DONE descriptor.  Same-process /
+ *                 pulls over xGMI on its one private copy stream and acks
+ *                 with a DONE descriptor: one copy kernel per progress pass
+ *                 (pull_kernels.h), or hipMemcpyAsync as a batch of one for
+ *                 a misaligned side or a host destination.  Same-process /
  *                 same-rank transfers skip IPC and use the raw pointer.
  *                 Consecutive partitions of one request go out as a RUN:
  *                 one descriptor, one pull, one DONE per acked range
@@ -49,241 +51,29 @@
 #include "done_ring.h"
 #include "layout.h"
 #include "part_run.h"
+#include "pull_kernels.h"
 #include "pull_plan.h"
+#include "shm_ring.h"
 #include "strided_plan.h"
 
 namespace mpix {
 
-/* Batched pull: one launch copies every partition/message that became
- * ready in the same progress pass (a 64 x 4 MiB partitioned step was
- * latency-bound at ~9 us per serialized launch+event).  The host plans the
- * batch (pull_plan.h): contiguous entries merge into one copy and every copy
- * is cut into tiles of 256 threads x U x 16 B.  Blocks grid-stride over the
- * TOTAL tile count, so they finish together whatever the size mix.  The
- * table travels by value in the kernel argument: no block reads host memory,
- * and there is no argument ring to recycle.  Per full tile a thread issues
- * its U 16-byte loads into independent registers before the first store
- * (U x 4 KiB in flight per block), through global-address-space pointers so
- * the accesses are global_*, not flat_*, and nontemporal by default: the
- * payload is touched once, and keeping it out of the caches is what
- * measured faster than the one-vector-per-thread kernel this replaces
- * (profiles/pull_stream_copy.md).  The partial last tile of a copy
- * and its n % 16 tail bytes take the slow branch.  No spin-wait in here, in
- * either variant (see maybe_switch_prio for why nothing may park on a
- * queue).  k_pull_multi carries no completion signal: its completion is the
- * event recorded behind the launch.  k_pull_multi_done (MPIX_PULL_DONE=word)
- * is the same copy followed by pull_signal_done, which nothing waits for
- * on the device either. */
-#define PULL_THREADS 256
-typedef unsigned int pull_v4 __attribute__((ext_vector_type(4)));
-typedef const __attribute__((address_space(1))) pull_v4 *pull_gsrc;
-typedef __attribute__((address_space(1))) pull_v4 *pull_gdst;
+/* ------------------------------------------------- knobs, each read once */
 
-template <bool NT>
-static __device__ __forceinline__ pull_v4 pull_ld(pull_gsrc p)
+/* a number; unset reads as `dflt` */
+static uint64_t env_u64(const char *name, uint64_t dflt)
 {
-    return NT ? __builtin_nontemporal_load(p) : *p;
+    const char *e = getenv(name);
+    return e ? (uint64_t)atoll(e) : dflt;
 }
 
-template <bool NT>
-static __device__ __forceinline__ void pull_st(pull_gdst p, pull_v4 v)
-{
-    if (NT)
-        __builtin_nontemporal_store(v, p);
-    else
-        *p = v;
-}
+static bool env_flag(const char *name) { return env_u64(name, 0) != 0; }
 
-/* Completion word (done_ring.h), device side.  Every block arrives at the
- * slot's counter once its own stores are out of the XCD's L2; the block
- * whose add is the last of the grid zeroes the counter for the slot's next
- * user and publishes the sequence number to the host word.  Nothing waits
- * and nothing spins.
- *  - each wave drains its own stores (vmcnt counts stores on gfx9), then the
- *    block barrier: thread 0 signals for all waves of the block;
- *  - agent-scope release before the add: nontemporal stores stay in the L2
- *    of the XCD, and the host word must not overtake them.  The wait behind
- *    the fence is written as asm so that it cannot be dropped;
- *  - the last arriver's add returned gridDim.x - 1, so every other block's
- *    release happened before it; its system-scope release store orders the
- *    counter reset and the word behind all of that. */
-struct PullDone {
-    uint32_t *counter; /* device memory, 0 between uses */
-    uint64_t *word;    /* pinned host memory */
-    uint64_t seq;
-};
-
-static __device__ __forceinline__ void pull_signal_done(const PullDone &d)
+/* MPIX_TRACE=1 (as in proxy.cpp) */
+static bool trace_on()
 {
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        const uint32_t before = __hip_atomic_fetch_add(
-            d.counter, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        if (before == gridDim.x - 1) {
-            __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
-            __hip_atomic_store(d.counter, 0u, __ATOMIC_RELAXED,
-                               __HIP_MEMORY_SCOPE_AGENT);
-            __hip_atomic_store(d.word, d.seq, __ATOMIC_RELEASE,
-                               __HIP_MEMORY_SCOPE_SYSTEM);
-        }
-    }
-}
-
-template <int U, bool NT>
-static __device__ __forceinline__ void pull_multi_body(const PullTable &t)
-{
-    constexpr uint64_t TILE = (uint64_t)PULL_THREADS * U * 16;
-    const uint64_t total = t.tile_end[t.ncopies - 1];
-    /* copy c holds global tiles [first, end); the table sits in the kernel
-     * argument and is re-read only when a block crosses into another copy */
-    uint32_t c = 0;
-    uint64_t first = 0, end = t.tile_end[0];
-    PullCopy cur = t.copy[0];
-    for (uint64_t tile = blockIdx.x; tile < total; tile += gridDim.x) {
-        if (tile >= end) {
-            do {
-                first = end;
-                end = t.tile_end[++c];
-            } while (tile >= end);
-            cur = t.copy[c];
-        }
-        const uint64_t off = (tile - first) * TILE;
-        const uint64_t left = cur.bytes - off;
-        pull_gsrc s = (pull_gsrc)(cur.src + off);
-        pull_gdst d = (pull_gdst)(cur.dst + off);
-        if (left >= TILE) {
-            pull_v4 r[U];
-#pragma unroll
-            for (int k = 0; k < U; k++)
-                r[k] = pull_ld<NT>(s + threadIdx.x + k * PULL_THREADS);
-#pragma unroll
-            for (int k = 0; k < U; k++)
-                pull_st<NT>(d + threadIdx.x + k * PULL_THREADS, r[k]);
-        } else {
-            const uint32_t nv = (uint32_t)(left / 16);
-            for (uint32_t v = threadIdx.x; v < nv; v += PULL_THREADS)
-                d[v] = s[v];
-            if (threadIdx.x < (uint32_t)(left & 15)) {
-                const uint64_t b = (uint64_t)nv * 16 + threadIdx.x;
-                ((__attribute__((address_space(1))) char *)d)[b] =
-                    ((const __attribute__((address_space(1))) char *)s)[b];
-            }
-        }
-    }
-}
-
-template <int U, bool NT>
-__global__ __launch_bounds__(PULL_THREADS) void k_pull_multi(const PullTable t)
-{
-    pull_multi_body<U, NT>(t);
-}
-
-template <int U, bool NT>
-__global__ __launch_bounds__(PULL_THREADS) void k_pull_multi_done(
-    const PullTable t, const PullDone d)
-{
-    pull_multi_body<U, NT>(t);
-    pull_signal_done(d);
-}
-
-/* Strided pull: the same launch shape for messages that are strided on
- * either side (strided_plan.h).  Work is indexed in message space in units
- * of the entry's granule, so a strided source lands straight in a strided
- * destination: no pack, no unpack, no staging buffer.  Consecutive lanes take
- * consecutive units, so lanes inside one run coalesce; a wave access made of
- * 128-byte segments streams at full rate, 64 lanes in 64 different rows do
- * not (4-byte runs are served correctly, not fast).  Per side a unit index
- * decomposes into (plane, run, offset) by two divisions whose reciprocals
- * the host prepared (a multiply and a shift each).  Granule 16 is the
- * vector path: one global_load_dwordx4 / global_store_dwordx4 per unit,
- * nontemporal, the U loads of a tile issued before its first store.  The
- * element path is the same walk with 8/4/2/1-byte accesses, 16/granule
- * rounds of it per tile.  Every unit is bounds-checked against the entry
- * (the partial last tile takes the same code).  WIDE is the variant with
- * 64-bit division, launched only when an entry has 2^31 units or more: it
- * is many times the code, so the common kernel does not carry it.  PARTS is
- * the variant for runs of partitions (an entry of k partitions, part strides
- * apart on each side): one more division per unit splits off the partition
- * number, shared by both sides since partitions have one size.  It is right
- * for every entry (one without a partition level has a quotient of 0), and
- * launched only when a batch holds a run entry, so plain strided messages
- * do not pay the third division. */
-template <typename T, int ROUNDS, bool WIDE, bool PARTS>
-static __device__ __forceinline__ void strided_tile(const StridedEntry &e,
-                                                    uint64_t unit0)
-{
-    typedef const __attribute__((address_space(1))) T *gsrc;
-    typedef __attribute__((address_space(1))) T *gdst;
-    constexpr int U = MPIX_STRIDED_UNROLL;
-    constexpr bool wide = WIDE;
-    constexpr bool parts = PARTS;
-#pragma unroll 1
-    for (int j = 0; j < ROUNDS; j++) {
-        T r[U];
-        int64_t doff[U];
-        bool ok[U];
-#pragma unroll
-        for (int k = 0; k < U; k++) {
-            const uint64_t u = unit0 +
-                (uint64_t)(j * U + k) * PULL_THREADS + threadIdx.x;
-            ok[k] = u < e.units;
-            if (ok[k]) {
-                int64_t soff;
-                strided_entry_offsets(e, u, wide, parts, &soff, &doff[k]);
-                r[k] = __builtin_nontemporal_load((gsrc)(e.src + soff));
-            }
-        }
-#pragma unroll
-        for (int k = 0; k < U; k++)
-            if (ok[k])
-                __builtin_nontemporal_store(r[k], (gdst)(e.dst + doff[k]));
-    }
-}
-
-template <bool WIDE, bool PARTS>
-static __device__ __forceinline__ void pull_strided_body(const StridedTable &t)
-{
-    const uint64_t total = t.tile_end[t.n - 1];
-    uint32_t c = 0;
-    uint64_t first = 0, end = t.tile_end[0];
-    StridedEntry cur = t.e[0];
-    for (uint64_t tile = blockIdx.x; tile < total; tile += gridDim.x) {
-        if (tile >= end) {
-            do {
-                first = end;
-                end = t.tile_end[++c];
-            } while (tile >= end);
-            cur = t.e[c];
-        }
-        /* units of this tile start at (tile bytes) >> glog */
-        const uint64_t unit0 = ((tile - first) * MPIX_STRIDED_TILE) >> cur.glog;
-        switch (cur.glog) {
-        case 4: strided_tile<pull_v4, 1, WIDE, PARTS>(cur, unit0); break;
-        case 3: strided_tile<uint64_t, 2, WIDE, PARTS>(cur, unit0); break;
-        case 2: strided_tile<uint32_t, 4, WIDE, PARTS>(cur, unit0); break;
-        case 1: strided_tile<uint16_t, 8, WIDE, PARTS>(cur, unit0); break;
-        default: strided_tile<uint8_t, 16, WIDE, PARTS>(cur, unit0); break;
-        }
-    }
-}
-
-template <bool WIDE, bool PARTS>
-__global__ __launch_bounds__(PULL_THREADS) void k_pull_strided(
-    const StridedTable t)
-{
-    pull_strided_body<WIDE, PARTS>(t);
-}
-
-/* MPIX_PULL_DONE=word: see pull_signal_done */
-template <bool WIDE, bool PARTS>
-__global__ __launch_bounds__(PULL_THREADS) void k_pull_strided_done(
-    const StridedTable t, const PullDone d)
-{
-    pull_strided_body<WIDE, PARTS>(t);
-    pull_signal_done(d);
+    static const bool v = env_flag("MPIX_TRACE");
+    return v;
 }
 
 /* Sender-push threshold for small DEVICE payloads: stage D2H into the shm
@@ -292,46 +82,26 @@ __global__ __launch_bounds__(PULL_THREADS) void k_pull_strided_done(
  * the two proxy-synchronous staging copies cost more than the round trip
  * they remove — profiles/r02_pingpong_devpush.json); kept off, tunable for
  * experiments with MPIX_DEV_PUSH_MAX=<bytes>. */
-static bool env_flag(const char *name)
-{
-    const char *e = getenv(name);
-    return e && atoi(e);
-}
-
-/* MPIX_TRACE=1, read once (as in proxy.cpp) */
-static bool trace_on()
-{
-    static const bool v = env_flag("MPIX_TRACE");
-    return v;
-}
-
 static uint64_t dev_push_max()
 {
-    static const uint64_t v = [] {
-        const char *e = getenv("MPIX_DEV_PUSH_MAX");
-        return e ? (uint64_t)atoll(e) : (uint64_t)0;
-    }();
+    static const uint64_t v = env_u64("MPIX_DEV_PUSH_MAX", 0);
     return v;
 }
 
-/* MPIX_PART_RUNS=0, read once: the sender announces every partition with a
- * descriptor of its own (runs of length 1 only), as before part_run.h.
- * An A/B inside one build, and the way tests drive both protocols. */
+/* MPIX_PART_RUNS=0: the sender announces every partition with a descriptor
+ * of its own (runs of length 1 only), as before part_run.h.  An A/B inside
+ * one build, and the way tests drive both protocols. */
 static bool part_runs_on()
 {
-    static const bool v = [] {
-        const char *e = getenv("MPIX_PART_RUNS");
-        return e ? atoi(e) != 0 : true;
-    }();
+    static const bool v = env_u64("MPIX_PART_RUNS", 1) != 0;
     return v;
 }
 
-/* MPIX_PULL_DONE=word|event, read once: how a pull kernel's completion
- * reaches the proxy.  event (default): an event recorded behind the launch
- * and tested with hipEventQuery in every pass.  word: the kernel's last
- * block stores a sequence number to pinned host memory (done_ring.h,
- * pull_signal_done); no event, no runtime call per pass.  The A/B is in
- * profiles/batch_handoffs.md. */
+/* MPIX_PULL_DONE=word|event: how a pull kernel's completion reaches the
+ * proxy.  event (default): an event recorded behind the launch and tested
+ * with hipEventQuery in every pass.  word: the kernel's last block stores a
+ * sequence number to pinned host memory (done_ring.h, pull_signal_done); no
+ * event, no runtime call per pass.  A/B: profiles/batch_handoffs.md. */
 static bool pull_done_word()
 {
     static const bool v = [] {
@@ -343,104 +113,68 @@ static bool pull_done_word()
     return v;
 }
 
-/* ------------------------------------------------------------- shm layout */
-
-static constexpr uint32_t RING_SLOTS_DEFAULT = 1024;
-static constexpr uint64_t CHUNK_BYTES = 64 * 1024;
-static constexpr uint32_t STAGE_CHUNKS_DEFAULT = 64; /* 4 MiB per pair */
-
-enum DescType : uint32_t {
-    DESC_HOST_CHUNK = 1, /* one staged chunk of a host-buffer message */
-    DESC_DEV_NOTIFY = 2, /* device-buffer message advertisement, or a run of
-                            partitions (count > 1) */
-    DESC_DONE       = 3, /* receiver ack for DESC_DEV_NOTIFY: all of it, or
-                            the range {partition, count} of a run */
-};
-
-enum DescFlags : uint32_t {
-    DESCF_PARTITIONED = 1u << 0,
-    DESCF_SELF_PTR    = 1u << 1, /* ipc field holds a raw pointer (same proc) */
-    DESCF_STRIDED     = 1u << 2, /* layout field holds the sender's layout */
-};
-
-struct alignas(64) Desc {
-    uint32_t type = 0;
-    uint32_t flags = 0;
-    uint64_t token = 0;       /* sender-side slot index */
-    int32_t src_world = -1;
-    int32_t tag = 0;
-    uint32_t comm_id = 0;
-    int32_t partition = -1;   /* a run (count > 1): its first partition */
-    uint64_t msg_bytes = 0;   /* a run: the size of ONE partition */
-    union {
-        uint64_t chunk_off = 0; /* HOST_CHUNK: offset of this chunk in the
-                                   msg */
-        int64_t part_stride;  /* DEV_NOTIFY of a partition: bytes between
-                                 partition p and p+1 at the SENDER (the
-                                 request's; not msg_bytes when there are
-                                 gaps).  Shares the word: a notify has no
-                                 chunks. */
-    };
-    uint64_t chunk_bytes = 0;
-    uint64_t stage_chunk = 0; /* HOST_CHUNK: chunk index in the stage ring */
-    uint8_t ipc[64] = {};     /* DEV_NOTIFY: hipIpcMemHandle_t (or raw ptr) */
-    uint64_t ipc_off = 0;
-    int32_t src_dev = -1;
-    uint32_t count = 0;       /* DEV_NOTIFY: partitions partition ..
-                                 partition+count-1 of one request, laid out
-                                 alike, part_stride apart (part_run.h);
-                                 DONE: that many partitions from `partition`
-                                 on are finished.  0 reads as 1. */
-    uint64_t t_seen_ns = 0;   /* DEV_NOTIFY: sender saw PENDING (MPIX_STATS=1;
-                                 steady clock, comparable across the node) */
-    MPIX_Layout layout = {};  /* DEV_NOTIFY / first HOST_CHUNK of a message
-                                 with DESCF_STRIDED: the sender's normalised
-                                 layout (both ends are the same build) */
-};
-static_assert(sizeof(Desc) == 192, "Desc layout"); /* layout took the pad */
-
-struct alignas(64) InboxHdr {
-    alignas(64) std::atomic<uint64_t> head;       /* producer (peer proxy) */
-    alignas(64) std::atomic<uint64_t> tail;       /* consumer (my proxy) */
-    alignas(64) std::atomic<uint64_t> stage_tail; /* chunks released by me */
-};
-
-struct ShmGeom {
-    uint32_t ring_slots;
-    uint32_t stage_chunks;
-    size_t inbox_bytes;   /* hdr + ring + stage, 64-aligned */
-    size_t segment_bytes; /* nranks inboxes */
-};
-
-static ShmGeom shm_geometry(int nranks)
+/* Kernel variant knobs; the defaults are the measured winners
+ * (profiles/pull_stream_copy.md).  MPIX_PULL_UNROLL = 4 (default) or 8
+ * vectors per thread and tile, or 1, which is the access pattern of the
+ * earlier kernel.  MPIX_PULL_NT=0 turns the nontemporal loads and stores
+ * off: the payload is touched once and is far larger than L2, and keeping
+ * it out of the caches is where the gain over the earlier kernel comes
+ * from (with plain accesses the tiled kernel is slower than that one).
+ * MPIX_PULL_BLOCKS caps the blocks of a launch (A/B in the same profile). */
+static int pull_unroll()
 {
-    ShmGeom g;
-    g.ring_slots = RING_SLOTS_DEFAULT;
-    if (const char *p = getenv("MPIX_SHM_RING")) g.ring_slots = atoi(p);
-    g.stage_chunks = STAGE_CHUNKS_DEFAULT;
-    if (const char *p = getenv("MPIX_SHM_STAGE_CHUNKS")) g.stage_chunks = atoi(p);
-    size_t b = sizeof(InboxHdr) + (size_t)g.ring_slots * sizeof(Desc) +
-               (size_t)g.stage_chunks * CHUNK_BYTES;
-    g.inbox_bytes = (b + 63) & ~(size_t)63;
-    g.segment_bytes = g.inbox_bytes * (size_t)nranks;
-    return g;
+    static const int v = [] {
+        const char *e = getenv("MPIX_PULL_UNROLL");
+        int u = e ? atoi(e) : 4;
+        return u == 1 || u == 8 ? u : 4;
+    }();
+    return v;
 }
 
-/* views into one inbox */
-struct InboxView {
-    InboxHdr *hdr;
-    Desc *ring;
-    char *stage;
-};
-
-static InboxView inbox_view(void *seg_base, const ShmGeom &g, int src)
+static bool pull_nontemporal()
 {
-    char *p = (char *)seg_base + (size_t)src * g.inbox_bytes;
-    InboxView v;
-    v.hdr = (InboxHdr *)p;
-    v.ring = (Desc *)(p + sizeof(InboxHdr));
-    v.stage = (char *)(v.ring + g.ring_slots);
+    static const bool v = env_u64("MPIX_PULL_NT", 1) != 0;
     return v;
+}
+
+static unsigned pull_max_blocks()
+{
+    static const int v = (int)env_u64("MPIX_PULL_BLOCKS", 1024);
+    return v > 0 ? (unsigned)v : 1024u;
+}
+
+/* ---------------------------------------------- receive-side completion */
+
+/* everything of the envelope but the partitioned kind and number */
+static bool envelope_match(const Op *op, uint32_t comm_id, int src, int tag)
+{
+    return op->comm_id == comm_id &&
+           (op->peer_world == MPI_ANY_SOURCE || op->peer_world == src) &&
+           (op->tag == MPI_ANY_TAG || op->tag == tag);
+}
+
+/* What receive `op` reports for a message of msg_bytes from world rank `src`:
+ * on SELF the source is rank 0; a longer message is cut and truncated. */
+static ChStatus recv_status(const Op *op, int src, int tag, uint64_t msg_bytes)
+{
+    ChStatus st;
+    st.src = (op->comm_id == 1) ? 0 : src;
+    st.tag = tag;
+    st.bytes = msg_bytes <= op->bytes ? msg_bytes : op->bytes;
+    st.err = msg_bytes > op->bytes ? MPI_ERR_TRUNCATE : MPI_SUCCESS;
+    return st;
+}
+
+static void complete_recv(Op *op, const ChStatus &st)
+{
+    op->ch_status = st;
+    op->ch_done.store(1, std::memory_order_release);
+}
+
+/* MPIX_STATS=1: the moment both sides of a pull had been seen PENDING */
+static uint64_t seen_ns(const Op *op, const Desc &d)
+{
+    return op->t_issue_ns > d.t_seen_ns ? op->t_issue_ns : d.t_seen_ns;
 }
 
 /* -------------------------------------------------------------- transport */
@@ -453,7 +187,7 @@ public:
 
     int init();
     void shutdown(); /* called from MPIX_Finalize before dtor */
-    ~NativeTransport() override;
+    ~NativeTransport() override { shutdown(); }
 
     int start(Op *op) override;
     void progress() override;
@@ -464,7 +198,6 @@ private:
     struct SendState {
         Op *op;
         uint64_t staged = 0;   /* bytes staged so far (host path) */
-        bool notified = false; /* DEV_NOTIFY emitted */
     };
     /* per-destination FIFO queues (preserves non-overtaking) */
     std::map<int, std::deque<SendState>> sendq_;
@@ -474,6 +207,9 @@ private:
         Op *op;       /* first (or only) op */
         Request *req; /* owner of a run (k > 1), else unused */
         RunAwait run;
+        Op *send_op(int32_t partition) const { /* the send of a partition */
+            return run.k == 1 ? op : &g_state->ops[req->part_idx[partition]];
+        }
     };
     std::unordered_map<uint64_t, AwaitDone> await_done_;
     /* pending DONE descriptors we could not emit (ring full) */
@@ -492,24 +228,14 @@ private:
         Op *op = nullptr;       /* matched recv, or null */
         std::vector<char> heap; /* unexpected host payload buffer */
         uint64_t got = 0;       /* host bytes received so far */
-        bool dev_copy_started = false;
         bool kind_mismatch = false; /* strided msg between host and device */
     };
     std::list<InboundMsg> inbound_;                 /* arrival order */
     std::unordered_map<uint64_t, InboundMsg *> inbound_by_token_;
     std::vector<Op *> posted_recvs_;                /* post order */
 
-    struct CopyInflight {
-        Op *op;
-        hipEvent_t ev;
-        int src;
-        uint64_t token;
-        int32_t partition;
-        ChStatus st;
-    };
-    std::list<CopyInflight> copies_;
-
-    /* pulls collected this progress pass, flushed as ONE kernel launch */
+    /* One pull.  Kernel pulls are collected over a progress pass and flushed
+     * as ONE launch; a hipMemcpyAsync pull is a batch of its own. */
     struct PendingPull {
         Op *op;             /* first (or only) receive */
         int src;
@@ -529,21 +255,23 @@ private:
         return j == 0 ? pp.op
                       : &g_state->ops[pp.op->req->part_idx[pp.partition + j]];
     }
-    static size_t pull_ops(const std::vector<PendingPull> &v, size_t n) {
+    static size_t pull_ops(const std::vector<PendingPull> &v) {
         size_t ops = 0;
-        for (size_t i = 0; i < n; i++) ops += v[i].k;
+        for (const PendingPull &pp : v) ops += pp.k;
         return ops;
     }
     void finish_pull(const PendingPull &pp, BatchStat *bs);
     std::vector<PendingPull> pend_pulls_;
+    /* what is in flight on a copy stream, in submission order */
     struct PullBatch {
         hipEvent_t ev = nullptr; /* event path; word path: only MPIX_STATS=1 */
         int done_slot = -1;   /* word path: slot of done_ring_, else -1 */
         hipStream_t cs = nullptr;
         uint64_t t_born_ns = 0;  /* word path: for the lost-signal guard */
         uint32_t passes = 0;     /* word path: passes that found no word */
-        uint64_t t_launch_ns = 0; /* MPIX_STATS=1 */
+        uint64_t t_launch_ns = 0; /* MPIX_STATS=1, contiguous kernel batches */
         bool first = false;   /* MPIX_STATS=1: first batch of the process */
+        bool memcpy_pull = false; /* hipMemcpyAsync, not a kernel */
         std::vector<PendingPull> items;
     };
     std::list<PullBatch> batches_;
@@ -557,9 +285,6 @@ private:
     std::atomic<uint64_t> *done_words_ = nullptr; /* host view */
     uint64_t *done_words_d_ = nullptr;            /* device view */
     uint32_t *done_counters_ = nullptr;
-    /* a batch on the word path: slot and kernel argument, or -1 (event
-     * path: MPIX_PULL_DONE=event, or the ring is full) */
-    int done_begin(PullDone *d);
     /* MPIX_STATS=1 with word: the event recorded all the same, kept after
      * the word was seen to measure word seen -> event seen */
     struct WordEvent {
@@ -568,9 +293,12 @@ private:
     };
     std::list<WordEvent> word_events_;
     bool batch_done(PullBatch &b, hipError_t *err);
-    void close_batch(PullBatch &b, hipStream_t cs, int slot, bool stats);
+    PullBatch &push_batch(std::vector<PendingPull> items, hipStream_t cs,
+                          int slot);
+    template <typename Launch>
+    PullBatch *submit_batch(std::vector<PendingPull> items, hipStream_t cs,
+                            const char *kernel, Launch launch);
     PullTable plan_{}; /* scratch of flush_pulls; passed by value */
-    void launch_pull(unsigned blocks, hipStream_t cs, const PullDone *done);
 
     /* strided pulls collected this progress pass: ONE k_pull_strided launch
      * per MPIX_STRIDED_BATCH of them, completed through batches_ like the
@@ -590,37 +318,37 @@ private:
 
     /* ---- shm ---- */
     ShmGeom geom_{};
-    std::string my_seg_name_;
+    void *map_segment(const char *name, bool create);
     std::vector<void *> seg_;       /* seg_[r] = rank r's segment base */
     std::vector<uint64_t> out_head_; /* producer-local head per dst */
     std::vector<uint64_t> out_stage_head_; /* producer-local chunk cursor */
     std::vector<uint64_t> in_tail_;  /* consumer-local tail per src */
 
     /* ---- hip ---- */
-    /* Copy-stream POOL.  Stream 0 is PLAIN and carries small pulls plus
-     * synchronous staging (lowest latency: a priority queue costs ~17 us
-     * extra half-RTT, ci_full2); streams 1..3 are created at GREATEST
-     * PRIORITY and carry large pulls concurrently — large partitioned
-     * transfers were latency-bound at ~9 us/partition serialized on one
-     * stream.  The high-priority set can never share a hardware queue
-     * with user streams (different priority = different queue), which
-     * matters beyond spin kernels: an unsatisfied hipStreamWaitValue32 is
-     * a queue-parking packet, so a SAME-priority copy stream that aliases
-     * a user stream's queue deadlocks exactly like the graph spin-kernel
-     * case (observed when a 4-plain-stream pool pushed total streams past
-     * the 4-queue pool: every transfer hung).  Stream 0 carries the same
-     * small residual aliasing risk as the original single-stream design
-     * (mitigated by the lazy priority upgrade below). */
-    static constexpr int N_COPY_STREAMS = 4;
-    hipStream_t copy_streams_[N_COPY_STREAMS] = {};
-    hipStream_t copy_plain0_ = nullptr; /* pre-upgrade stream 0 (kept) */
+    /* ONE plain copy stream carries every pull and the synchronous staging
+     * copies (memcpy_auto); it is upgraded to greatest priority, lazily, once
+     * a spin-wait kernel was ever emitted (maybe_switch_prio).  Batched
+     * pulls serialize on it at HBM rate, and there are NO standing extra
+     * streams: each extra hardware queue, even another process's, adds tens
+     * of us to every wait on the device (36.5 -> ~55 us 2-process half-RTT).
+     * copy_big_ (MPIX_COPY_PRIO_STREAM=1) is the experiment that opts one
+     * back in, for batches above MPIX_COPY_POOL_MIN bytes. */
+    hipStream_t copy_stream_ = nullptr;
+    hipStream_t copy_retired_ = nullptr; /* the plain stream after the switch,
+                                            kept alive for what is on it */
+    hipStream_t copy_big_ = nullptr;
     bool prio_switched_ = false;
-    static uint64_t pool_min_bytes() {
-        static const uint64_t v = [] {
-            const char *e = getenv("MPIX_COPY_POOL_MIN");
-            return e ? (uint64_t)atoll(e) : (uint64_t)(256 << 10);
-        }();
-        return v;
+    /* a new greatest-priority stream, or nullptr */
+    static hipStream_t prio_stream() {
+        int lo = 0, hi = 0;
+        hipStream_t ps = nullptr;
+        if (hipDeviceGetStreamPriorityRange(&lo, &hi) == hipSuccess &&
+            hi != lo &&
+            hipStreamCreateWithPriority(&ps, hipStreamNonBlocking, hi) ==
+                hipSuccess)
+            return ps;
+        (void)hipGetLastError();
+        return nullptr;
     }
 
     /* The copy stream must never share a hardware queue with a stream that
@@ -642,37 +370,22 @@ private:
             !g_state->spin_wait_kernels.load(std::memory_order_acquire))
             return;
         prio_switched_ = true;
-        int lo = 0, hi = 0;
-        hipStream_t ps = nullptr;
-        if (hipDeviceGetStreamPriorityRange(&lo, &hi) == hipSuccess &&
-            hi != lo &&
-            hipStreamCreateWithPriority(&ps, hipStreamNonBlocking, hi) ==
-                hipSuccess) {
-            copy_plain0_ = copy_streams_[0];
-            copy_streams_[0] = ps;
-        } else {
-            (void)hipGetLastError();
+        if (hipStream_t ps = prio_stream()) {
+            copy_retired_ = copy_stream_;
+            copy_stream_ = ps;
         }
     }
-    /* stream for an independent pull: small payloads ride the plain
-     * stream 0 (latency), large ones rotate over the priority set 1..3
-     * (bandwidth; per-message ordering is by the event recorded on the
-     * same stream as the copy) */
+    /* stream for `bytes` of copy: the copy stream (ordering per message is
+     * by what is recorded on the same stream as its copy) */
     hipStream_t copy_stream(uint64_t bytes) {
+        static const uint64_t pool_min =
+            env_u64("MPIX_COPY_POOL_MIN", 256 << 10);
         maybe_switch_prio();
-        if (bytes <= pool_min_bytes() || copy_streams_[1] == nullptr)
-            return copy_streams_[0];
-        return copy_streams_[1];
-    }
-    /* fixed stream for synchronous staging (memcpy_auto) */
-    hipStream_t copy_stream0() {
-        maybe_switch_prio();
-        return copy_streams_[0];
+        return bytes > pool_min && copy_big_ ? copy_big_ : copy_stream_;
     }
     std::vector<hipEvent_t> event_pool_;
     std::unordered_map<std::string, void *> ipc_open_;   /* handle -> ptr */
-    std::unordered_map<const void *, std::pair<void *, hipIpcMemHandle_t>>
-        ipc_get_;                                        /* buf base -> handle */
+    std::unordered_map<const void *, hipIpcMemHandle_t> ipc_get_; /* by base */
 
     Bootstrap *boot_ = nullptr;
 
@@ -687,39 +400,40 @@ private:
     InboxView out_box(int dst) { return inbox_view(seg_[dst], geom_, rank_); }
 
     bool ring_has_space(int dst, uint64_t need) {
-        InboxView v = out_box(dst);
-        uint64_t tail = v.hdr->tail.load(std::memory_order_acquire);
-        return out_head_[dst] + need - tail <= geom_.ring_slots;
+        return mpix::ring_has_space(out_box(dst), geom_, out_head_[dst], need);
     }
     void emit_desc(int dst, const Desc &d) {
-        InboxView v = out_box(dst);
-        uint64_t h = out_head_[dst];
-        v.ring[h % geom_.ring_slots] = d;
-        v.hdr->head.store(h + 1, std::memory_order_release);
-        out_head_[dst] = h + 1;
-    }
-    uint64_t stage_free_chunks(int dst) {
-        InboxView v = out_box(dst);
-        uint64_t st = v.hdr->stage_tail.load(std::memory_order_acquire);
-        return geom_.stage_chunks - (out_stage_head_[dst] - st);
+        ring_emit(out_box(dst), geom_, &out_head_[dst], d);
     }
 
-    hipEvent_t get_event();
-    void put_event(hipEvent_t ev);
+    hipEvent_t get_event() {
+        hipEvent_t ev = nullptr;
+        if (event_pool_.empty()) {
+            (void)hipEventCreateWithFlags(&ev, hipEventDisableTiming);
+        } else {
+            ev = event_pool_.back();
+            event_pool_.pop_back();
+        }
+        return ev;
+    }
+    void put_event(hipEvent_t ev) { event_pool_.push_back(ev); }
 
-    int progress_sends();
-    int drain_inbox(int src);
-    int progress_copies();
+    void progress_sends();
+    void drain_inbox(int src);
+    void progress_copies();
     void flush_pulls();
     void flush_strided();
     void fail_kind_mismatch(InboundMsg &m);
     void handle_desc(int src, const Desc &d, const char *stage_base);
     bool try_run_fast_path(int src, const Desc &d, uint32_t k);
+    Desc desc_for(const Op *op, DescType type) const;
+    bool emit_done(int dst, uint64_t token, int32_t first, uint32_t count);
     void ack(int src, uint64_t token, int32_t first, uint32_t count);
     void handle_done(uint64_t token, int32_t first, uint32_t count);
     void try_match_new_inbound(InboundMsg &m);
     void attach(InboundMsg &m, Op *op);
     void start_dev_copy(InboundMsg &m);
+    void fail_dev_recv(InboundMsg &m, const ChStatus &st);
     void finish_host_recv(InboundMsg &m);
     void deliver_chunk(InboundMsg &m, const Desc &d, const char *src_chunk);
     void erase_inbound(InboundMsg *m);
@@ -731,42 +445,49 @@ private:
 
 /* ------------------------------------------------------------------- init */
 
-int NativeTransport::init()
+/* Map segment `name`; create: make it first (ours), and zero it. */
+void *NativeTransport::map_segment(const char *name, bool create)
 {
-    boot_ = make_bootstrap(rank_, size_, mpi_mode_);
-    if (!boot_) return -1;
-
-    geom_ = shm_geometry(size_);
-
-    /* create my segment */
-    char name[96];
-    unsigned seed = (unsigned)getpid() * 2654435761u + (unsigned)rank_;
-    snprintf(name, sizeof(name), "/mpix-r%d-%d-%x", rank_, (int)getpid(),
-             rand_r(&seed));
-    my_seg_name_ = name;
-    int fd = shm_open(name, O_CREAT | O_EXCL | O_RDWR, 0600);
+    int fd = shm_open(name, create ? O_CREAT | O_EXCL | O_RDWR : O_RDWR, 0600);
     if (fd < 0) {
         MPIX_ERR("shm_open(%s) failed", name);
-        return -1;
+        return nullptr;
     }
-    if (ftruncate(fd, (off_t)geom_.segment_bytes) != 0) {
+    if (create && ftruncate(fd, (off_t)geom_.segment_bytes) != 0) {
         MPIX_ERR("ftruncate(%zu) failed", geom_.segment_bytes);
         close(fd);
-        return -1;
+        return nullptr;
     }
     void *base = mmap(nullptr, geom_.segment_bytes, PROT_READ | PROT_WRITE,
                       MAP_SHARED, fd, 0);
     close(fd);
     if (base == MAP_FAILED) {
-        MPIX_ERR("mmap own segment failed");
-        return -1;
+        MPIX_ERR("mmap(%s) failed", name);
+        return nullptr;
     }
-    memset(base, 0, geom_.segment_bytes);
+    if (create) memset(base, 0, geom_.segment_bytes);
+    return base;
+}
 
-    /* exchange names, open peers */
+int NativeTransport::init()
+{
+    boot_ = make_bootstrap(rank_, size_, mpi_mode_);
+    if (!boot_) return -1;
+
+    geom_ = shm_geometry(
+        size_, (uint32_t)env_u64("MPIX_SHM_RING", RING_SLOTS_DEFAULT),
+        (uint32_t)env_u64("MPIX_SHM_STAGE_CHUNKS", STAGE_CHUNKS_DEFAULT));
+
+    /* create my segment */
     struct Blob { char name[96]; };
     Blob mine{};
-    snprintf(mine.name, sizeof(mine.name), "%s", name);
+    unsigned seed = (unsigned)getpid() * 2654435761u + (unsigned)rank_;
+    snprintf(mine.name, sizeof(mine.name), "/mpix-r%d-%d-%x", rank_,
+             (int)getpid(), rand_r(&seed));
+    void *base = map_segment(mine.name, true);
+    if (base == nullptr) return -1;
+
+    /* exchange names, open peers */
     std::vector<Blob> all(size_);
     if (boot_->allgather(&mine, all.data(), sizeof(Blob)) != 0) {
         MPIX_ERR("bootstrap allgather failed");
@@ -776,23 +497,12 @@ int NativeTransport::init()
     seg_[rank_] = base;
     for (int r = 0; r < size_; r++) {
         if (r == rank_) continue;
-        int pfd = shm_open(all[r].name, O_RDWR, 0600);
-        if (pfd < 0) {
-            MPIX_ERR("shm_open(peer %s) failed", all[r].name);
-            return -1;
-        }
-        void *pb = mmap(nullptr, geom_.segment_bytes, PROT_READ | PROT_WRITE,
-                        MAP_SHARED, pfd, 0);
-        close(pfd);
-        if (pb == MAP_FAILED) {
-            MPIX_ERR("mmap peer segment failed");
-            return -1;
-        }
-        seg_[r] = pb;
+        seg_[r] = map_segment(all[r].name, false);
+        if (seg_[r] == nullptr) return -1;
     }
     /* everyone mapped everything -> segments can be unlinked */
     boot_->barrier();
-    shm_unlink(my_seg_name_.c_str());
+    shm_unlink(mine.name);
 
     out_head_.assign(size_, 0);
     out_stage_head_.assign(size_, 0);
@@ -801,18 +511,11 @@ int NativeTransport::init()
     strided_div64_ = env_flag("MPIX_STRIDED_DIV64");
 
     if (have_gpu_) {
-        if (hipStreamCreateWithFlags(&copy_streams_[0],
-                                     hipStreamNonBlocking) != hipSuccess) {
+        if (hipStreamCreateWithFlags(&copy_stream_, hipStreamNonBlocking) !=
+            hipSuccess) {
             MPIX_ERR("copy stream create failed");
             return -1;
         }
-        /* NO standing second stream: every additional hardware queue
-         * (even per another process) oversubscribes the device's HW
-         * scheduler and adds tens of us to every wait — a standing
-         * priority stream alone pushed the 2-process 8-B half-RTT from
-         * 36.5 to ~55 us.  Batched pulls serialize on stream 0 at HBM
-         * rate, so extra streams buy nothing; MPIX_COPY_PRIO_STREAM=1
-         * opts a standing priority stream back in for experiments. */
         if (pull_done_word()) {
             void *w = nullptr, *wd = nullptr, *c = nullptr;
             const size_t wbytes =
@@ -832,20 +535,8 @@ int NativeTransport::init()
             done_counters_ = (uint32_t *)c;
             done_word_ = true;
         }
-        if (env_flag("MPIX_COPY_PRIO_STREAM")) {
-            int lo = 0, hi = 0;
-            if (hipDeviceGetStreamPriorityRange(&lo, &hi) == hipSuccess &&
-                hi != lo) {
-                if (hipStreamCreateWithPriority(&copy_streams_[1],
-                                                hipStreamNonBlocking, hi) !=
-                    hipSuccess) {
-                    (void)hipGetLastError();
-                    copy_streams_[1] = nullptr;
-                }
-            } else {
-                (void)hipGetLastError();
-            }
-        }
+        /* the standing priority stream, for experiments only */
+        if (env_flag("MPIX_COPY_PRIO_STREAM")) copy_big_ = prio_stream();
     }
     return 0;
 }
@@ -868,36 +559,16 @@ void NativeTransport::shutdown()
     done_words_d_ = nullptr;
     done_counters_ = nullptr;
     done_word_ = false;
-    for (int i = 0; i < N_COPY_STREAMS; i++) {
-        if (copy_streams_[i]) (void)hipStreamDestroy(copy_streams_[i]);
-        copy_streams_[i] = nullptr;
+    for (hipStream_t *s : {&copy_stream_, &copy_big_, &copy_retired_}) {
+        if (*s) (void)hipStreamDestroy(*s);
+        *s = nullptr;
     }
-    if (copy_plain0_) (void)hipStreamDestroy(copy_plain0_);
-    copy_plain0_ = nullptr;
     for (int r = 0; r < (int)seg_.size(); r++)
         if (seg_[r]) munmap(seg_[r], geom_.segment_bytes);
     seg_.clear();
     delete boot_;
     boot_ = nullptr;
 }
-
-NativeTransport::~NativeTransport() { shutdown(); }
-
-/* ------------------------------------------------------------------ events */
-
-hipEvent_t NativeTransport::get_event()
-{
-    if (!event_pool_.empty()) {
-        hipEvent_t ev = event_pool_.back();
-        event_pool_.pop_back();
-        return ev;
-    }
-    hipEvent_t ev = nullptr;
-    (void)hipEventCreateWithFlags(&ev, hipEventDisableTiming);
-    return ev;
-}
-
-void NativeTransport::put_event(hipEvent_t ev) { event_pool_.push_back(ev); }
 
 /* ------------------------------------------------------------------- start */
 
@@ -930,14 +601,11 @@ int NativeTransport::start(Op *op)
 
 bool NativeTransport::match(const Op *op, const Desc &d, int src) const
 {
-    if (op->comm_id != d.comm_id) return false;
-    bool want_part = (op->kind == OpKind::PRECV_PART);
-    bool is_part = (d.flags & DESCF_PARTITIONED) != 0;
-    if (want_part != is_part) return false;
-    if (want_part && op->partition != d.partition) return false;
-    if (op->peer_world != MPI_ANY_SOURCE && op->peer_world != src) return false;
-    if (op->tag != MPI_ANY_TAG && op->tag != d.tag) return false;
-    return true;
+    const bool want_part = (op->kind == OpKind::PRECV_PART);
+    const bool is_part = (d.flags & DESCF_PARTITIONED) != 0;
+    return want_part == is_part &&
+           (!want_part || op->partition == d.partition) &&
+           envelope_match(op, d.comm_id, src, d.tag);
 }
 
 /* ---------------------------------------------------------------- progress */
@@ -953,31 +621,36 @@ void NativeTransport::progress()
     /* retry queued DONE acks */
     for (size_t i = 0; i < pending_done_.size();) {
         const PendingDone pd = pending_done_[i];
-        if (ring_has_space(pd.dst, 1)) {
-            Desc d;
-            d.type = DESC_DONE;
-            d.token = pd.token;
-            d.src_world = rank_;
-            d.partition = pd.first;
-            d.count = pd.count;
-            emit_desc(pd.dst, d);
+        if (emit_done(pd.dst, pd.token, pd.first, pd.count))
             pending_done_.erase(pending_done_.begin() + i);
-        } else {
+        else
             i++;
-        }
     }
 }
 
 void NativeTransport::complete_send_buffered(Op *op)
 {
-    op->ch_status.src = (op->comm_id == 1) ? 0 : rank_;
-    op->ch_status.tag = op->tag;
-    op->ch_status.bytes = op->bytes;
-    op->ch_status.err = MPI_SUCCESS;
+    op->ch_status = ChStatus{(op->comm_id == 1) ? 0 : rank_, op->tag,
+                             op->bytes, MPI_SUCCESS};
     op->ch_done.store(1, std::memory_order_release);
 }
 
-int NativeTransport::progress_sends()
+/* what a DEV_NOTIFY and a HOST_CHUNK of `op` have in common */
+Desc NativeTransport::desc_for(const Op *op, DescType type) const
+{
+    Desc d;
+    d.type = type;
+    d.flags = (op->kind == OpKind::PSEND_PART) ? DESCF_PARTITIONED : 0;
+    d.token = (uint64_t)(op - g_state->ops);
+    d.src_world = rank_;
+    d.tag = op->tag;
+    d.comm_id = op->comm_id;
+    d.partition = op->partition;
+    d.msg_bytes = op->bytes;
+    return d;
+}
+
+void NativeTransport::progress_sends()
 {
     for (auto &kv : sendq_) {
         int dst = kv.first;
@@ -1001,16 +674,8 @@ int NativeTransport::progress_sends()
                                        o->kind == OpKind::PSEND_PART,
                                        o->buf_is_device, o->strided};
                     }, dev_push_max());
-                Desc d;
-                d.type = DESC_DEV_NOTIFY;
+                Desc d = desc_for(op, DESC_DEV_NOTIFY);
                 d.count = (uint32_t)k;
-                d.flags = (op->kind == OpKind::PSEND_PART) ? DESCF_PARTITIONED : 0;
-                d.token = (uint64_t)(op - g_state->ops);
-                d.src_world = rank_;
-                d.tag = op->tag;
-                d.comm_id = op->comm_id;
-                d.partition = op->partition;
-                d.msg_bytes = op->bytes;
                 d.src_dev = dev_;
                 d.t_seen_ns = op->t_issue_ns;
                 /* the request's, never inferred from msg_bytes: contiguous
@@ -1045,9 +710,9 @@ int NativeTransport::progress_sends()
                             q.pop_front();
                             continue;
                         }
-                        it = ipc_get_.emplace(base, std::make_pair(base, h)).first;
+                        it = ipc_get_.emplace(base, h).first;
                     }
-                    memcpy(d.ipc, &it->second.second, sizeof(hipIpcMemHandle_t));
+                    memcpy(d.ipc, &it->second, sizeof(hipIpcMemHandle_t));
                     d.ipc_off = (uint64_t)((char *)op->buf - (char *)base);
                 }
                 /* before the descriptor is visible: a self-loopback ack
@@ -1065,14 +730,15 @@ int NativeTransport::progress_sends()
             /* host-staged path */
             bool stalled = false;
             while (ss.staged < op->bytes || op->bytes == 0) {
-                if (!ring_has_space(dst, 1) || stage_free_chunks(dst) == 0) {
+                InboxView v = out_box(dst);
+                if (!ring_has_space(dst, 1) ||
+                    stage_free_chunks(v, geom_, out_stage_head_[dst]) == 0) {
                     stalled = true;
                     break;
                 }
                 uint64_t chunk_idx = out_stage_head_[dst] % geom_.stage_chunks;
                 uint64_t n = op->bytes - ss.staged;
                 if (n > CHUNK_BYTES) n = CHUNK_BYTES;
-                InboxView v = out_box(dst);
                 if (n > 0) {
                     char *stage_dst = v.stage + chunk_idx * CHUNK_BYTES;
                     const char *payload = (const char *)op->buf + ss.staged;
@@ -1084,15 +750,7 @@ int NativeTransport::progress_sends()
                     else
                         memcpy(stage_dst, payload, n);
                 }
-                Desc d;
-                d.type = DESC_HOST_CHUNK;
-                d.flags = (op->kind == OpKind::PSEND_PART) ? DESCF_PARTITIONED : 0;
-                d.token = (uint64_t)(op - g_state->ops);
-                d.src_world = rank_;
-                d.tag = op->tag;
-                d.comm_id = op->comm_id;
-                d.partition = op->partition;
-                d.msg_bytes = op->bytes;
+                Desc d = desc_for(op, DESC_HOST_CHUNK);
                 d.chunk_off = ss.staged;
                 d.chunk_bytes = n;
                 if (op->strided && ss.staged == 0) {
@@ -1110,23 +768,17 @@ int NativeTransport::progress_sends()
             q.pop_front();
         }
     }
-    return 0;
 }
 
-int NativeTransport::drain_inbox(int src)
+void NativeTransport::drain_inbox(int src)
 {
     InboxView v = my_inbox(src);
-    uint64_t head = v.hdr->head.load(std::memory_order_acquire);
-    uint64_t tail = in_tail_[src];
+    const uint64_t head = ring_head(v);
     int budget = 64;
-    while (tail < head && budget-- > 0) {
-        const Desc &d = v.ring[tail % geom_.ring_slots];
-        handle_desc(src, d, v.stage);
-        tail++;
-        v.hdr->tail.store(tail, std::memory_order_release);
-        in_tail_[src] = tail;
+    while (in_tail_[src] < head && budget-- > 0) {
+        handle_desc(src, ring_front(v, geom_, in_tail_[src]), v.stage);
+        ring_pop(v, &in_tail_[src]);
     }
-    return 0;
 }
 
 void NativeTransport::handle_desc(int src, const Desc &d, const char *stage_base)
@@ -1182,8 +834,7 @@ void NativeTransport::handle_desc(int src, const Desc &d, const char *stage_base
         else
             MPIX_ERR("chunk for unknown msg token %lu", (unsigned long)d.token);
         /* release the stage credit unconditionally (no credit leaks) */
-        InboxView v = my_inbox(src);
-        v.hdr->stage_tail.fetch_add(1, std::memory_order_release);
+        stage_release(my_inbox(src));
         if (m != nullptr && m->got >= m->d.msg_bytes) finish_host_recv(*m);
         return;
     }
@@ -1210,14 +861,24 @@ void NativeTransport::handle_done(uint64_t token, int32_t first,
                  a.run.remaining, (unsigned long)token);
         return;
     }
-    if (a.run.k == 1) {
-        complete_send_buffered(a.op);
-    } else {
-        for (uint32_t j = 0; j < count; j++)
-            complete_send_buffered(
-                &g_state->ops[a.req->part_idx[first + (int32_t)j]]);
-    }
+    for (uint32_t j = 0; j < count; j++) /* a single message: count is 1 */
+        complete_send_buffered(a.send_op(first + (int32_t)j));
     if (r == RUN_ACK_LAST) await_done_.erase(it);
+}
+
+/* A DONE for rank `dst` through the ring; false: no slot free, nothing sent */
+bool NativeTransport::emit_done(int dst, uint64_t token, int32_t first,
+                                uint32_t count)
+{
+    if (!ring_has_space(dst, 1)) return false;
+    Desc d;
+    d.type = DESC_DONE;
+    d.token = token;
+    d.src_world = rank_;
+    d.partition = first;
+    d.count = count;
+    emit_desc(dst, d);
+    return true;
 }
 
 /* The receiver's end: tell rank `src` that partitions [first, first+count)
@@ -1228,21 +889,10 @@ void NativeTransport::handle_done(uint64_t token, int32_t first,
 void NativeTransport::ack(int src, uint64_t token, int32_t first,
                           uint32_t count)
 {
-    if (src == rank_) {
+    if (src == rank_)
         handle_done(token, first, count);
-        return;
-    }
-    if (ring_has_space(src, 1)) {
-        Desc d;
-        d.type = DESC_DONE;
-        d.token = token;
-        d.src_world = rank_;
-        d.partition = first;
-        d.count = count;
-        emit_desc(src, d);
-    } else {
+    else if (!emit_done(src, token, first, count))
         pending_done_.push_back(PendingDone{src, token, first, count});
-    }
 }
 
 /* A run of k partitions whose receives are all posted, in order, as the
@@ -1266,10 +916,8 @@ bool NativeTransport::try_run_fast_path(int src, const Desc &d, uint32_t k)
         posted_recvs_.size(),
         [&](size_t i) {
             const Op *o = posted_recvs_[i];
-            const bool env =
-                o->kind == OpKind::PRECV_PART && o->comm_id == d.comm_id &&
-                (o->peer_world == MPI_ANY_SOURCE || o->peer_world == src) &&
-                (o->tag == MPI_ANY_TAG || o->tag == d.tag);
+            const bool env = o->kind == OpKind::PRECV_PART &&
+                             envelope_match(o, d.comm_id, src, d.tag);
             RunRecv r{o->req, o->partition, o->bytes, (uintptr_t)o->buf, env,
                       o->buf_is_device, o->strided};
             /* the receiver's own distance between partitions */
@@ -1296,15 +944,11 @@ bool NativeTransport::try_run_fast_path(int src, const Desc &d, uint32_t k)
         return false;
     posted_recvs_.erase(posted_recvs_.begin() + first,
                         posted_recvs_.begin() + first + (long)k);
-    ChStatus st;
-    st.src = (op->comm_id == 1) ? 0 : src;
-    st.tag = d.tag;
-    st.bytes = d.msg_bytes;
-    st.err = MPI_SUCCESS;
-    uint64_t seen = op->t_issue_ns > d.t_seen_ns ? op->t_issue_ns
-                                                 : d.t_seen_ns;
-    const PendingPull pp{op, src, d.token, st, op->buf, sp,
-                         (uint64_t)k * d.msg_bytes, seen, d.partition, k};
+    /* every receive of the range is msg_bytes long: nothing is truncated */
+    const PendingPull pp{op, src, d.token,
+                         recv_status(op, src, d.tag, d.msg_bytes), op->buf, sp,
+                         (uint64_t)k * d.msg_bytes, seen_ns(op, d),
+                         d.partition, k};
     g_state->run_fast_msgs += k;
     if (plain) {
         pend_pulls_.push_back(pp);
@@ -1330,8 +974,9 @@ bool NativeTransport::try_run_fast_path(int src, const Desc &d, uint32_t k)
     return true;
 }
 
-/* Every receive of a pull gets its status and ch_done (the per-partition
- * flag transitions stay with the proxy walk); the sender gets ONE ack. */
+/* The sender gets ONE ack, then every receive of the pull gets its status
+ * and ch_done (the per-partition flag transitions stay with the proxy
+ * walk). */
 void NativeTransport::finish_pull(const PendingPull &pp, BatchStat *bs)
 {
     if (bs != nullptr && pp.src == rank_) {
@@ -1342,10 +987,7 @@ void NativeTransport::finish_pull(const PendingPull &pp, BatchStat *bs)
         if (it != await_done_.end()) {
             const AwaitDone &a = it->second;
             for (uint32_t j = 0; j < pp.k; j++) {
-                Op *so = a.run.k == 1
-                    ? a.op
-                    : &g_state->ops[a.req->part_idx[pp.partition + (int32_t)j]];
-                so->stat_batch = bs;
+                a.send_op(pp.partition + (int32_t)j)->stat_batch = bs;
                 bs->left_send++;
             }
         }
@@ -1354,8 +996,7 @@ void NativeTransport::finish_pull(const PendingPull &pp, BatchStat *bs)
     for (uint32_t j = 0; j < pp.k; j++) {
         Op *op = pull_op(pp, j);
         op->stat_batch = bs;
-        op->ch_status = pp.st;
-        op->ch_done.store(1, std::memory_order_release);
+        complete_recv(op, pp.st);
     }
 }
 
@@ -1375,7 +1016,6 @@ void NativeTransport::try_match_new_inbound(InboundMsg &m)
 
 void NativeTransport::attach(InboundMsg &m, Op *op)
 {
-    op->ch_priv = &m;
     m.op = op;
     if (m.d.type == DESC_DEV_NOTIFY) {
         start_dev_copy(m);
@@ -1426,18 +1066,12 @@ void NativeTransport::deliver_chunk(InboundMsg &m, const Desc &d,
 void NativeTransport::finish_host_recv(InboundMsg &m)
 {
     if (m.op == nullptr) return; /* stays buffered until a recv posts */
-    Op *op = m.op;
-    op->ch_status.src = (op->comm_id == 1) ? 0 : m.src;
-    op->ch_status.tag = m.d.tag;
-    op->ch_status.bytes =
-        m.d.msg_bytes <= op->bytes ? m.d.msg_bytes : op->bytes;
-    op->ch_status.err =
-        m.d.msg_bytes > op->bytes ? MPI_ERR_TRUNCATE : MPI_SUCCESS;
+    ChStatus st = recv_status(m.op, m.src, m.d.tag, m.d.msg_bytes);
     if (m.kind_mismatch) {
-        op->ch_status.bytes = 0;
-        op->ch_status.err = MPI_ERR_TYPE;
+        st.bytes = 0;
+        st.err = MPI_ERR_TYPE;
     }
-    op->ch_done.store(1, std::memory_order_release);
+    complete_recv(m.op, st);
     erase_inbound(&m);
 }
 
@@ -1482,186 +1116,134 @@ void *NativeTransport::map_remote(const Desc &d)
     return (char *)base + d.ipc_off;
 }
 
+/* A matched device message that will move no data: the receive completes
+ * with `st`, and the sender is still acked so that it does not hang. */
+void NativeTransport::fail_dev_recv(InboundMsg &m, const ChStatus &st)
+{
+    complete_recv(m.op, st);
+    ack(m.src, m.d.token, m.d.partition, 1);
+    erase_inbound(&m);
+}
+
 void NativeTransport::start_dev_copy(InboundMsg &m)
 {
     Op *op = m.op;
     void *src = map_remote(m.d);
-    ChStatus st;
-    st.src = (op->comm_id == 1) ? 0 : m.src;
-    st.tag = m.d.tag;
-    st.bytes = m.d.msg_bytes <= op->bytes ? m.d.msg_bytes : op->bytes;
-    st.err = m.d.msg_bytes > op->bytes ? MPI_ERR_TRUNCATE : MPI_SUCCESS;
+    ChStatus st = recv_status(op, m.src, m.d.tag, m.d.msg_bytes);
     if (src == nullptr) {
         st.err = MPI_ERR_OTHER;
-        op->ch_status = st;
-        op->ch_done.store(1, std::memory_order_release);
-        /* still ack so the sender does not hang */
-        ack(m.src, m.d.token, m.d.partition, 1);
-        erase_inbound(&m);
+        fail_dev_recv(m, st);
         return;
     }
-    uint64_t n = st.bytes;
-    hipError_t e = hipSuccess;
     const bool strided = op->strided || (m.d.flags & DESCF_STRIDED) != 0;
     if (strided && !op->buf_is_device) {
         fail_kind_mismatch(m);
         st.bytes = 0;
         st.err = MPI_ERR_TYPE;
-        op->ch_status = st;
-        op->ch_done.store(1, std::memory_order_release);
-        ack(m.src, m.d.token, m.d.partition, 1);
-        erase_inbound(&m);
+        fail_dev_recv(m, st);
         return;
     }
-    if (strided && n > 0) {
-        /* defer: every strided pull that matched in this progress pass goes
-         * out in ONE k_pull_strided launch (flush_strided).  n is a multiple
-         * of the granule: it is the length of one of the two layouts, and the
-         * granule divides the runs of both. */
-        uint64_t seen = op->t_issue_ns > m.d.t_seen_ns ? op->t_issue_ns
-                                                       : m.d.t_seen_ns;
-        PendingStrided ps;
-        ps.pp = PendingPull{op, m.src, m.d.token, st, op->buf, src, n, seen,
-                            m.d.partition, 1};
-        ps.sl = (m.d.flags & DESCF_STRIDED) ? m.d.layout
-                                            : layout_contiguous(m.d.msg_bytes);
-        ps.dl = op->strided ? op->layout : layout_contiguous(op->bytes);
-        pend_strided_.push_back(ps);
-        m.dev_copy_started = true;
-        erase_inbound(&m);
-        return;
-    }
+    const uint64_t n = st.bytes;
+    const PendingPull pp{op, m.src, m.d.token, st, op->buf, src, n,
+                         seen_ns(op, m.d), m.d.partition, 1};
     /* The shader pull path requires (a) a device destination — dereferencing
      * a pageable host pointer from a kernel faults on non-XNACK systems —
      * and (b) 16-byte alignment on both sides (user buffers can be
-     * arbitrarily offset, e.g. partitioned slices).  Everything else rides
-     * hipMemcpyAsync (SDMA / runtime blit). */
-    /* pull kernel is deadlock-safe in both copy-stream phases: before the
-     * priority switch no spin-wait kernel exists anywhere; after it the
-     * copy stream owns its hardware queue (see copy_stream()) */
-    bool kernel_ok = op->buf_is_device &&
-                     ((((uintptr_t)op->buf) | ((uintptr_t)src)) & 15) == 0;
-    if (n > 0 && kernel_ok) {
+     * arbitrarily offset, e.g. partitioned slices); a strided pull goes by
+     * its granule instead.  Everything else rides hipMemcpyAsync (SDMA /
+     * runtime blit).  A pull kernel is deadlock-safe in both copy-stream
+     * phases: before the priority switch no spin-wait kernel exists; after
+     * it the copy stream owns its hardware queue (see maybe_switch_prio) */
+    const bool kernel_ok = op->buf_is_device &&
+        ((((uintptr_t)op->buf) | ((uintptr_t)src)) & 15) == 0;
+    if (n > 0 && (strided || kernel_ok)) {
         /* defer: every pull that matched in this progress pass goes out in
-         * ONE k_pull_multi launch (flush_pulls) */
-        uint64_t seen = op->t_issue_ns > m.d.t_seen_ns ? op->t_issue_ns
-                                                       : m.d.t_seen_ns;
-        pend_pulls_.push_back(PendingPull{op, m.src, m.d.token, st,
-                                          op->buf, src, n, seen,
-                                          m.d.partition, 1});
-        m.dev_copy_started = true;
+         * ONE k_pull_multi launch (flush_pulls), every strided one in ONE
+         * k_pull_strided launch (flush_strided).  There n is a multiple of
+         * the granule: it is the length of one of the two layouts, and the
+         * granule divides the runs of both. */
+        if (strided) {
+            PendingStrided ps;
+            ps.pp = pp;
+            ps.sl = (m.d.flags & DESCF_STRIDED)
+                        ? m.d.layout : layout_contiguous(m.d.msg_bytes);
+            ps.dl = op->strided ? op->layout : layout_contiguous(op->bytes);
+            pend_strided_.push_back(ps);
+        } else {
+            pend_pulls_.push_back(pp);
+        }
         erase_inbound(&m);
         return;
     }
+    /* a batch of one, always on the event path: a runtime copy cannot store
+     * a completion word.  t_launch_ns stays 0 */
     hipStream_t cs = copy_stream(n);
-    if (n > 0) {
-        e = hipMemcpyAsync(op->buf, src, n, hipMemcpyDefault, cs);
-    }
+    hipError_t e = hipSuccess;
+    if (n > 0) e = hipMemcpyAsync(op->buf, src, n, hipMemcpyDefault, cs);
     if (e != hipSuccess) {
         MPIX_ERR("hipMemcpyAsync(pull %lu B) failed: %s", (unsigned long)n,
                  hipGetErrorString(e));
         st.err = MPI_ERR_OTHER;
-        op->ch_status = st;
-        op->ch_done.store(1, std::memory_order_release);
-        ack(m.src, m.d.token, m.d.partition, 1);
-        erase_inbound(&m);
+        fail_dev_recv(m, st);
         return;
     }
     if (trace_on())
         fprintf(stderr, "[mpix trace] pull start %lu B via memcpyAsync "
                 "(dst=%p src=%p)\n", (unsigned long)n, op->buf, src);
-    hipEvent_t ev = get_event();
-    hipError_t erec = hipEventRecord(ev, cs);
-    if (erec != hipSuccess)
-        MPIX_ERR("hipEventRecord(pull) failed: %s", hipGetErrorString(erec));
-    copies_.push_back(CopyInflight{op, ev, m.src, m.d.token, m.d.partition,
-                                   st});
-    m.dev_copy_started = true;
+    push_batch({pp}, cs, -1).memcpy_pull = true;
     erase_inbound(&m);
 }
 
-/* Kernel variant knobs, read once; the defaults are the measured winners
- * (profiles/pull_stream_copy.md).  MPIX_PULL_UNROLL = 4 (default) or 8
- * vectors per thread and tile, or 1, which is the access pattern of the
- * earlier kernel.  MPIX_PULL_NT=0 turns the nontemporal loads and stores
- * off: the payload is touched once and is far larger than L2, and keeping
- * it out of the caches is where the gain over the earlier kernel comes
- * from (with plain accesses the tiled kernel is slower than that one). */
-static int pull_unroll()
+/* What follows a successful launch or copy on `cs`: its batch, the last of
+ * batches_.  The word path (slot >= 0) records no event (with MPIX_STATS=1
+ * it does, to measure what the event would have cost). */
+NativeTransport::PullBatch &NativeTransport::push_batch(
+    std::vector<PendingPull> items, hipStream_t cs, int slot)
 {
-    static const int v = [] {
-        const char *e = getenv("MPIX_PULL_UNROLL");
-        int u = e ? atoi(e) : 4;
-        return u == 1 || u == 8 ? u : 4;
-    }();
-    return v;
-}
-
-static bool pull_nontemporal()
-{
-    static const bool v = [] {
-        const char *e = getenv("MPIX_PULL_NT");
-        return e ? atoi(e) != 0 : true;
-    }();
-    return v;
-}
-
-template <int U>
-static void launch_pull_u(bool nt, unsigned blocks, hipStream_t cs,
-                          const PullTable &t, const PullDone *done)
-{
-    if (done != nullptr) {
-        if (nt)
-            hipLaunchKernelGGL((k_pull_multi_done<U, true>), dim3(blocks),
-                               dim3(PULL_THREADS), 0, cs, t, *done);
-        else
-            hipLaunchKernelGGL((k_pull_multi_done<U, false>), dim3(blocks),
-                               dim3(PULL_THREADS), 0, cs, t, *done);
-        return;
-    }
-    if (nt)
-        hipLaunchKernelGGL((k_pull_multi<U, true>), dim3(blocks),
-                           dim3(PULL_THREADS), 0, cs, t);
-    else
-        hipLaunchKernelGGL((k_pull_multi<U, false>), dim3(blocks),
-                           dim3(PULL_THREADS), 0, cs, t);
-}
-
-void NativeTransport::launch_pull(unsigned blocks, hipStream_t cs,
-                                  const PullDone *done)
-{
-    const bool nt = pull_nontemporal();
-    switch (pull_unroll()) {
-    case 1: launch_pull_u<1>(nt, blocks, cs, plan_, done); break;
-    case 8: launch_pull_u<8>(nt, blocks, cs, plan_, done); break;
-    default: launch_pull_u<4>(nt, blocks, cs, plan_, done); break;
-    }
-}
-
-int NativeTransport::done_begin(PullDone *d)
-{
-    if (!done_word_) return -1;
-    uint64_t seq = 0;
-    const int slot = done_acquire(&done_ring_, &seq);
-    if (slot < 0) return -1; /* ring full: this batch takes the event path */
-    d->counter = done_counters_ + (size_t)slot * DONE_COUNTER_STRIDE;
-    d->word = done_words_d_ + (size_t)slot * DONE_WORD_STRIDE;
-    d->seq = seq;
-    return slot;
-}
-
-/* What follows a successful launch: the word path records no event (with
- * MPIX_STATS=1 it does, to measure what the event would have cost). */
-void NativeTransport::close_batch(PullBatch &b, hipStream_t cs, int slot,
-                                  bool stats)
-{
+    batches_.emplace_back();
+    PullBatch &b = batches_.back();
+    b.items = std::move(items);
     b.done_slot = slot;
     b.cs = cs;
     if (slot >= 0) b.t_born_ns = now_ns();
-    if (slot < 0 || stats) {
+    if (slot < 0 || (g_state != nullptr && g_state->stats)) {
         b.ev = get_event();
-        (void)hipEventRecord(b.ev, cs);
+        hipError_t e = hipEventRecord(b.ev, cs);
+        if (e != hipSuccess)
+            MPIX_ERR("hipEventRecord(pull) failed: %s", hipGetErrorString(e));
     }
+    return b;
+}
+
+/* The second half of a flush: `items` go out as one launch on `cs`.
+ * launch(done) issues the kernel (done: the argument of the completion
+ * word, or nullptr on the event path) and returns the launch's error.
+ * Returns the batch; or nullptr: the launch failed, and every item was
+ * finished with MPI_ERR_OTHER. */
+template <typename Launch>
+NativeTransport::PullBatch *NativeTransport::submit_batch(
+    std::vector<PendingPull> items, hipStream_t cs, const char *kernel,
+    Launch launch)
+{
+    /* word path: a slot and the kernel's argument for it; event path
+     * (MPIX_PULL_DONE=event, or the ring is full): slot -1 */
+    PullDone done{nullptr, nullptr, 0};
+    const int slot = done_word_ ? done_acquire(&done_ring_, &done.seq) : -1;
+    if (slot >= 0) {
+        done.counter = done_counters_ + (size_t)slot * DONE_COUNTER_STRIDE;
+        done.word = done_words_d_ + (size_t)slot * DONE_WORD_STRIDE;
+    }
+    const hipError_t e = launch(slot >= 0 ? &done : nullptr);
+    if (e != hipSuccess) {
+        MPIX_ERR("%s launch failed: %s", kernel, hipGetErrorString(e));
+        if (slot >= 0) done_release(&done_ring_, slot);
+        for (PendingPull &pp : items) {
+            pp.st.err = MPI_ERR_OTHER;
+            finish_pull(pp, nullptr);
+        }
+        return nullptr;
+    }
+    return &push_batch(std::move(items), cs, slot);
 }
 
 void NativeTransport::flush_pulls()
@@ -1672,8 +1254,7 @@ void NativeTransport::flush_pulls()
         PullSeg segs[MPIX_PULL_BATCH];
         size_t n = pend_pulls_.size();
         if (n > MPIX_PULL_BATCH) n = MPIX_PULL_BATCH;
-        uint64_t total = 0;
-        uint64_t t_first = UINT64_MAX;
+        uint64_t total = 0, t_first = UINT64_MAX;
         for (size_t i = 0; i < n; i++) {
             const PendingPull &pp = pend_pulls_[i];
             segs[i] = PullSeg{pp.dst, pp.csrc, pp.n};
@@ -1682,56 +1263,45 @@ void NativeTransport::flush_pulls()
         }
         plan_pulls(segs, n, tile_bytes, &plan_);
         hipStream_t cs = copy_stream(total);
-        static const unsigned max_blocks = [] {
-            const char *e = getenv("MPIX_PULL_BLOCKS");
-            /* cap on blocks; A/B in profiles/pull_stream_copy.md */
-            return e && atoi(e) > 0 ? (unsigned)atoi(e) : 1024u;
-        }();
         uint64_t tiles = pull_total_tiles(plan_);
-        unsigned blocks = tiles < max_blocks ? (unsigned)tiles : max_blocks;
-        PullDone done;
-        const int slot = done_begin(&done);
-        const uint64_t t_call = stats ? now_ns() : 0;
-        launch_pull(blocks, cs, slot >= 0 ? &done : nullptr);
-        hipError_t e = hipGetLastError();
-        const uint64_t t_rec = stats ? now_ns() : 0;
-        if (e != hipSuccess) {
-            MPIX_ERR("k_pull_multi launch failed: %s", hipGetErrorString(e));
-            if (slot >= 0) done_release(&done_ring_, slot);
-            for (size_t i = 0; i < n; i++) {
-                pend_pulls_[i].st.err = MPI_ERR_OTHER;
-                finish_pull(pend_pulls_[i], nullptr);
-            }
-            pend_pulls_.erase(pend_pulls_.begin(), pend_pulls_.begin() + n);
-            continue;
-        }
-        PullBatch b;
-        close_batch(b, cs, slot, stats);
+        unsigned blocks = tiles < pull_max_blocks() ? (unsigned)tiles
+                                                    : pull_max_blocks();
+        std::vector<PendingPull> items(pend_pulls_.begin(),
+                                       pend_pulls_.begin() + n);
+        pend_pulls_.erase(pend_pulls_.begin(), pend_pulls_.begin() + n);
+        uint64_t t_call = 0, t_rec = 0;
+        PullBatch *b = submit_batch(
+            std::move(items), cs, "k_pull_multi", [&](const PullDone *done) {
+                t_call = stats ? now_ns() : 0;
+                launch_pull(plan_, pull_unroll(), pull_nontemporal(), blocks,
+                            cs, done);
+                const hipError_t e = hipGetLastError();
+                t_rec = stats ? now_ns() : 0;
+                return e;
+            });
+        if (b == nullptr) continue;
         if (stats) {
             State *s = g_state;
-            b.t_launch_ns = now_ns();
+            b->t_launch_ns = now_ns();
             const uint64_t call = t_rec - t_call;
             if (!s->bleg_first_seen) {
                 /* loads the code object: reported apart from the means */
-                s->bleg_first_seen = b.first = true;
-                s->bleg_first_wait_ns = b.t_launch_ns - t_first;
+                s->bleg_first_seen = b->first = true;
+                s->bleg_first_wait_ns = b->t_launch_ns - t_first;
                 s->bleg_first_call_ns = call;
-                s->bleg_first_rec_ns = b.t_launch_ns - t_rec;
-                s->bleg_first_items = pull_ops(pend_pulls_, n);
+                s->bleg_first_rec_ns = b->t_launch_ns - t_rec;
+                s->bleg_first_items = pull_ops(b->items);
             } else {
-                s->bleg_wait_ns += b.t_launch_ns - t_first;
+                s->bleg_wait_ns += b->t_launch_ns - t_first;
                 s->bleg_call_ns += call;
                 if (call < s->bleg_call_min_ns) s->bleg_call_min_ns = call;
                 if (call > s->bleg_call_max_ns) s->bleg_call_max_ns = call;
-                s->bleg_rec_ns += b.t_launch_ns - t_rec;
+                s->bleg_rec_ns += b->t_launch_ns - t_rec;
                 s->bleg_n++;
-                s->bleg_items += pull_ops(pend_pulls_, n);
+                s->bleg_items += pull_ops(b->items);
                 s->bleg_copies += plan_.ncopies;
             }
         }
-        b.items.assign(pend_pulls_.begin(), pend_pulls_.begin() + n);
-        pend_pulls_.erase(pend_pulls_.begin(), pend_pulls_.begin() + n);
-        batches_.push_back(std::move(b));
         if (trace_on())
             fprintf(stderr, "[mpix trace] pull batch n=%zu copies=%u "
                     "tiles=%lu total=%lu B\n", n, plan_.ncopies,
@@ -1746,6 +1316,7 @@ void NativeTransport::flush_strided()
         size_t n = pend_strided_.size();
         if (n > MPIX_STRIDED_BATCH) n = MPIX_STRIDED_BATCH;
         uint64_t total = 0;
+        std::vector<PendingPull> items;
         for (size_t i = 0; i < n; i++) {
             const PendingStrided &ps = pend_strided_[i];
             segs[i] = StridedSeg{ps.pp.dst, ps.pp.csrc, ps.pp.n, ps.sl, ps.dl};
@@ -1755,7 +1326,9 @@ void NativeTransport::flush_strided()
                 segs[i].d_part_stride = ps.d_part_stride;
             }
             total += ps.pp.n;
+            items.push_back(ps.pp);
         }
+        pend_strided_.erase(pend_strided_.begin(), pend_strided_.begin() + n);
         plan_strided(segs, n, strided_div64_, &splan_);
         /* same stream choice as flush_pulls: a contiguous batch of this
          * pass and this launch go back to back on the copy stream */
@@ -1764,44 +1337,15 @@ void NativeTransport::flush_strided()
         unsigned blocks = tiles < 1024 ? (unsigned)tiles : 1024u;
         const bool wide = strided_plan_wide(splan_);
         const bool parts = strided_plan_parts(splan_);
-        PullDone done;
-        const int slot = done_begin(&done);
-#define MPIX_LAUNCH_STRIDED(W, P)                                            \
-        do {                                                                  \
-            if (slot >= 0)                                                    \
-                hipLaunchKernelGGL((k_pull_strided_done<W, P>), dim3(blocks), \
-                                   dim3(PULL_THREADS), 0, cs, splan_, done);  \
-            else                                                              \
-                hipLaunchKernelGGL((k_pull_strided<W, P>), dim3(blocks),      \
-                                   dim3(PULL_THREADS), 0, cs, splan_);        \
-        } while (0)
-        if (wide && parts)
-            MPIX_LAUNCH_STRIDED(true, true);
-        else if (wide)
-            MPIX_LAUNCH_STRIDED(true, false);
-        else if (parts)
-            MPIX_LAUNCH_STRIDED(false, true);
-        else
-            MPIX_LAUNCH_STRIDED(false, false);
-#undef MPIX_LAUNCH_STRIDED
-        hipError_t e = hipGetLastError();
-        if (e != hipSuccess) {
-            MPIX_ERR("k_pull_strided launch failed: %s", hipGetErrorString(e));
-            if (slot >= 0) done_release(&done_ring_, slot);
-            for (size_t i = 0; i < n; i++) {
-                pend_strided_[i].pp.st.err = MPI_ERR_OTHER;
-                finish_pull(pend_strided_[i].pp, nullptr);
-            }
-            pend_strided_.erase(pend_strided_.begin(),
-                                pend_strided_.begin() + n);
+        /* t_launch_ns stays 0: the batch legs of MPIX_STATS count plain
+         * pulls */
+        if (submit_batch(std::move(items), cs, "k_pull_strided",
+                         [&](const PullDone *done) {
+                             launch_strided(splan_, wide, parts, blocks, cs,
+                                            done);
+                             return hipGetLastError();
+                         }) == nullptr)
             continue;
-        }
-        PullBatch b; /* t_launch_ns stays 0: the batch legs of MPIX_STATS
-                        count plain pulls */
-        close_batch(b, cs, slot, g_state != nullptr && g_state->stats);
-        for (size_t i = 0; i < n; i++) b.items.push_back(pend_strided_[i].pp);
-        pend_strided_.erase(pend_strided_.begin(), pend_strided_.begin() + n);
-        batches_.push_back(std::move(b));
         if (trace_on())
             fprintf(stderr, "[mpix trace] strided pull batch n=%zu tiles=%lu "
                     "total=%lu B wide=%d parts=%d\n", n, (unsigned long)tiles,
@@ -1809,7 +1353,7 @@ void NativeTransport::flush_strided()
     }
 }
 
-/* Is the batch's kernel finished?  *err: hipSuccess, or why its ops fail.
+/* Is the batch's work finished?  *err: hipSuccess, or why its ops fail.
  * Event path: hipEventQuery.  Word path: a plain acquire load of the slot's
  * host word, no runtime call.  A kernel that dies never stores its word, so
  * for a batch older than a second the stream is asked, once per 4096 passes
@@ -1849,7 +1393,7 @@ bool NativeTransport::batch_done(PullBatch &b, hipError_t *err)
     return true;
 }
 
-int NativeTransport::progress_copies()
+void NativeTransport::progress_copies()
 {
     for (auto it = word_events_.begin(); it != word_events_.end();) {
         if (hipEventQuery(it->ev) == hipErrorNotReady) {
@@ -1867,11 +1411,11 @@ int NativeTransport::progress_copies()
             ++it;
             continue;
         }
+        if (it->memcpy_pull && trace_on())
+            fprintf(stderr, "[mpix trace] pull done (e=%d)\n", (int)e);
         BatchStat *bs = nullptr;
         if (it->t_launch_ns) {
-            bs = new BatchStat{now_ns(),
-                               (int)pull_ops(it->items, it->items.size()),
-                               it->first};
+            bs = new BatchStat{now_ns(), (int)pull_ops(it->items), it->first};
             if (it->first)
                 g_state->bleg_first_kernel_ns = bs->t_ev_ns - it->t_launch_ns;
             else
@@ -1885,29 +1429,13 @@ int NativeTransport::progress_copies()
                 g_state->bleg_whole_ns.push_back(
                     (uint32_t)(bs->t_ev_ns - it->t_launch_ns));
         }
+        /* ack the sender, then complete the receives */
         for (PendingPull &pp : it->items) {
             if (e != hipSuccess) pp.st.err = MPI_ERR_OTHER;
             finish_pull(pp, bs);
         }
         it = batches_.erase(it);
     }
-    for (auto it = copies_.begin(); it != copies_.end();) {
-        hipError_t e = hipEventQuery(it->ev);
-        if (e == hipErrorNotReady) {
-            ++it;
-            continue;
-        }
-        if (e != hipSuccess) it->st.err = MPI_ERR_OTHER;
-        if (trace_on())
-            fprintf(stderr, "[mpix trace] pull done (e=%d)\n", (int)e);
-        put_event(it->ev);
-        /* ack the sender, then complete the recv */
-        ack(it->src, it->token, it->partition, 1);
-        it->op->ch_status = it->st;
-        it->op->ch_done.store(1, std::memory_order_release);
-        it = copies_.erase(it);
-    }
-    return 0;
 }
 
 void NativeTransport::erase_inbound(InboundMsg *m)
@@ -1939,12 +1467,11 @@ int NativeTransport::memcpy_auto(void *dst, const void *src, size_t n)
      * on hipStreamWaitValue32 waiting for THIS proxy to make progress
      * (deadlock observed with MPIX_DEV_PUSH_MAX; the reference documents
      * the same hazard class, README.md:140-150). */
-    bool dd = ptr_is_device(dst);
-    if (!dd && !ptr_is_device(src)) {
+    if (!ptr_is_device(dst) && !ptr_is_device(src)) {
         memcpy(dst, src, n);
         return 0;
     }
-    hipStream_t cs = copy_stream0();
+    hipStream_t cs = copy_stream(0); /* always the copy stream itself */
     if (hipMemcpyAsync(dst, src, n, hipMemcpyDefault, cs) != hipSuccess)
         return -1;
     return hipStreamSynchronize(cs) == hipSuccess ? 0 : -1;

@@ -180,3 +180,75 @@ def test_empty_message(mpix_env):
     dst = sentinel(2 * PAD)
     exchange(mpix_env, [((src, 16), (dst, PAD), 0)])
     check_sentinels(dst, [])
+
+
+def test_device_host_plain(mpix_env):
+    """4100 B (a 4-byte tail behind the last vector) between device and host
+    memory, host waits.  Device -> host: a pull whose destination no kernel
+    may touch, so it rides hipMemcpyAsync.  Host -> device: chunks staged
+    through shared memory and copied in on the copy stream."""
+    import numpy as np
+    torch = _torch()
+    mpix = mpix_env
+    stream = torch.cuda.current_stream()
+    n = 4100
+    want = pattern(n, 16).cpu().numpy()
+
+    src = pattern(n + 16).clone()
+    host = np.full(n + 2 * PAD, SENT, dtype=np.uint8)
+    torch.cuda.synchronize()
+    rr = mpix.irecv_enqueue((host.ctypes.data + PAD, n), source=0, tag=31)
+    rs = mpix.isend_enqueue((src.data_ptr() + 16, n), dest=0, tag=31,
+                            stream=stream)
+    st = mpix.wait(rr)
+    mpix.wait(rs)
+    assert st["error"] == 0 and st["count_bytes"] == n
+    assert (host[PAD:PAD + n] == want).all()
+    assert (host[:PAD] == SENT).all() and (host[PAD + n:] == SENT).all()
+
+    hsrc = np.concatenate([np.zeros(16, dtype=np.uint8), want])
+    dst = sentinel(n + 2 * PAD)
+    torch.cuda.synchronize()
+    rs = mpix.isend_enqueue((hsrc.ctypes.data + 16, n), dest=0, tag=32)
+    rr = mpix.irecv_enqueue((dst.data_ptr() + PAD, n), source=0, tag=32,
+                            stream=stream)
+    st = mpix.wait(rr)
+    mpix.wait(rs)
+    torch.cuda.synchronize()
+    assert st["error"] == 0 and st["count_bytes"] == n
+    assert torch.equal(dst[PAD:PAD + n], pattern(n, 16))
+    check_sentinels(dst, [(PAD, n)])
+
+
+def _misaligned_pair(rank, size):
+    import torch
+    import mpix
+    mpix.init()
+    try:
+        peer = 1 - rank
+        n = 16400
+        src = pattern(n + 4, 100 * rank).clone()
+        dst = sentinel(n + 2 * PAD)
+        assert (src.data_ptr() + 4) % 16 == 4
+        assert (dst.data_ptr() + PAD + 4) % 16 == 4
+        stream = torch.cuda.current_stream()
+        torch.cuda.synchronize()
+        rr = mpix.irecv_enqueue((dst.data_ptr() + PAD + 4, n), source=peer,
+                                tag=7, stream=stream)
+        rs = mpix.isend_enqueue((src.data_ptr() + 4, n), dest=peer, tag=7,
+                                stream=stream)
+        mpix.waitall_enqueue([rr, rs], stream=stream)
+        torch.cuda.synchronize()
+        assert torch.equal(dst[PAD + 4:PAD + 4 + n],
+                           pattern(n, 100 * peer + 4))
+        check_sentinels(dst, [(PAD + 4, n)])
+    finally:
+        mpix.finalize()
+
+
+def test_misaligned_two_ranks():
+    """test_misaligned_buffers between two processes: the hipMemcpyAsync
+    pull reads the peer's memory, and its ack goes back through the peer's
+    descriptor ring and not through the loopback shortcut."""
+    from conftest import run_ranks
+    run_ranks(2, _misaligned_pair, timeout=120)
