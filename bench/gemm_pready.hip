@@ -2,18 +2,26 @@
  * hand-written CDNA4 MFMA bf16 GEMM (BASELINE.json config 5).
  *
  * Each rank computes C = A x B (bf16 in, fp32 accumulate, bf16 out) with a
- * gfx950 MFMA kernel (v_mfma_f32_16x16x32_bf16, 128x128 tiles staged through
- * LDS, XCD-aware workgroup swizzle) and partition-sends C to its right
- * neighbor: C's row bands are the NPARTS partitions of a persistent
- * MPIX_Psend.  When the LAST workgroup of a band finishes its C tile it
- * publishes the band from inside the kernel (system-release ticket counter
- * + MPIX_Pready), so the proxy streams finished bands over xGMI while the
- * rest of the GEMM is still running.  The receiver MPIX_Waits and verifies
- * a sample of C against a host fp32 reference.
+ * gfx950 MFMA kernel (v_mfma_f32_16x16x32_bf16; the default variant 4 has
+ * 256x256 tiles with BK=64 staged into two LDS buffers by global_load_lds,
+ * an XCD-aware workgroup remap and a grouped block order; variants 2 and 3
+ * have 128x128 tiles, 5 and 6 other pipelines on the 256x256 tile) and
+ * partition-sends C to its right neighbor: C's row bands are the NPARTS
+ * partitions of a persistent MPIX_Psend.  When the LAST workgroup of a band
+ * finishes its C tile it publishes the band from inside the kernel
+ * (system-release ticket counter + MPIX_Pready), so the proxy streams
+ * finished bands over xGMI while the rest of the GEMM is still running.
+ * The receiver MPIX_Waits; every VERIFY_EVERY iterations an xor checksum of
+ * what it received is compared with the sender's C.
  *
  * Reports overlapped time vs GEMM-then-send, GEMM TFLOP/s, and effective
  * bandwidth.  Run: mpiexec -np N bench/bin/gemm_pready [M N K iters]
- * (--check: small-size full verification of the MFMA kernel itself).
+ *
+ * --check [M N K [nparts]] (default 256 256 512, one band per tile row)
+ * verifies the kernel instead of timing it: ALL of C against a float64
+ * host reference (bench/gemm_check.h) with publish off, then again with the
+ * bands published and sent, Crecv byte-identical to the sender's C and every
+ * band counter complete.  See run_check below.
  *
  * Publish protocol per §6 Guideline 16 of the CDNA4 guide: plain C stores
  * -> s_waitcnt vmcnt(0) -> __syncthreads -> lane0 system release fence +
@@ -31,6 +39,8 @@
 
 #include "mpix/mpix.h"
 #include "mpix/mpix_device.h"
+
+#include "gemm_check.h"
 
 #define NPARTS 64
 
@@ -893,16 +903,227 @@ __global__ void k_poison(uint32_t *buf, int nparts, size_t part_words)
     if (p < nparts) buf[(size_t)p * part_words] = 0xDEADBEEFu;
 }
 
-static void host_gemm_ref(const std::vector<float> &A,
-                          const std::vector<float> &B, std::vector<float> &C,
-                          int M, int N, int K)
+/* -------------------------------------------------------------- --check
+ * The kernel against the float64 reference of gemm_check.h, in both data
+ * modes (unit only while K <= 256, where it is bit-exact).
+ *
+ * A and B sit inside larger allocations whose guard regions (one tile row
+ * before and after) hold bf16 NaN: a K-tile or a tile row read past the end
+ * poisons the result.  C and Crecv sit between sentinel guards that must
+ * survive, and both are filled with NaN before every launch.
+ *
+ * Pass A launches with publish = 0 and checks all of C.  Pass B launches
+ * with publish = 1 and sends C as nparts bands to the right neighbour (the
+ * process itself when alone) through the same requests as the timed mode:
+ * C is checked again, Crecv must be byte-identical to the sender's C (a band
+ * published before its last tile was stored arrives with NaN in it), and
+ * every band counter must stand at blocks_per_band.  With several ranks the
+ * receiver also regenerates the left rank's inputs from its seed and checks
+ * Crecv against that reference.
+ *
+ * One JSON line per pass and mode; returns the number of failed passes. */
+static bool all_equal(const uint16_t *p, size_t n, uint16_t v)
 {
-    for (int i = 0; i < M; i++)
-        for (int j = 0; j < N; j++) {
-            float s = 0.f;
-            for (int k = 0; k < K; k++) s += A[i * K + k] * B[k * N + j];
-            C[i * N + j] = s;
+    for (size_t i = 0; i < n; i++)
+        if (p[i] != v) return false;
+    return true;
+}
+
+static int run_check(int rank, int size, int M, int N, int K, int nparts)
+{
+    namespace gc = gemm_check;
+    const uint16_t SENTINEL = 0xA5A5u;
+    int right = (rank + 1) % size, left = (rank - 1 + size) % size;
+    int blocks_per_band = (M / nparts / BM) * (N / BN);
+    int grid = (M / BM) * (N / BN);
+
+    size_t an = (size_t)M * K, bn = (size_t)K * N, cn = (size_t)M * N;
+    size_t ga = (size_t)BM * K; /* guards: one tile row of each operand */
+#if MPIX_GEMM_VARIANT >= 4
+    size_t gb = (size_t)BN * K;
+#else
+    size_t gb = (size_t)BK * N;
+#endif
+    size_t gcn = (size_t)BM * N;
+    uint16_t *Aall, *Ball, *Call, *Rall;
+    HIP(hipMalloc(&Aall, (an + 2 * ga) * sizeof(uint16_t)));
+    HIP(hipMalloc(&Ball, (bn + 2 * gb) * sizeof(uint16_t)));
+    HIP(hipMalloc(&Call, (cn + 2 * gcn) * sizeof(uint16_t)));
+    HIP(hipMalloc(&Rall, (cn + 2 * gcn) * sizeof(uint16_t)));
+    HIP(hipMemset(Aall, 0xFF, (an + 2 * ga) * sizeof(uint16_t)));
+    HIP(hipMemset(Ball, 0xFF, (bn + 2 * gb) * sizeof(uint16_t)));
+    HIP(hipMemset(Call, 0xA5, (cn + 2 * gcn) * sizeof(uint16_t)));
+    HIP(hipMemset(Rall, 0xA5, (cn + 2 * gcn) * sizeof(uint16_t)));
+    bf16 *A = (bf16 *)(Aall + ga), *B = (bf16 *)(Ball + gb);
+    bf16 *C = (bf16 *)(Call + gcn), *Crecv = (bf16 *)(Rall + gcn);
+    uint32_t *band_cnt;
+    HIP(hipMalloc(&band_cnt, nparts * sizeof(uint32_t)));
+    hipStream_t st;
+    HIP(hipStreamCreate(&st));
+
+    MPIX_Request ps, pr;
+    int count = (int)(cn / nparts);
+    CHECK(MPIX_Psend_init(C, nparts, count, MPI_SHORT, right, 21,
+                          MPI_COMM_WORLD, MPI_INFO_NULL, &ps) == 0);
+    CHECK(MPIX_Precv_init(Crecv, nparts, count, MPI_SHORT, left, 21,
+                          MPI_COMM_WORLD, MPI_INFO_NULL, &pr) == 0);
+    MPIX_Prequest dps;
+    CHECK(MPIX_Prequest_create(ps, &dps) == 0);
+
+    std::vector<uint16_t> hA(an), hBt(bn), hB, hC(cn + 2 * gcn),
+        hR(cn + 2 * gcn), leftC(cn);
+    std::vector<uint32_t> hcnt(nparts);
+    gc::Reference ref, ref_left;
+    int failed = 0;
+
+    for (gc::Mode mode : {gc::UNIT, gc::UNIFORM}) {
+        if (mode == gc::UNIT && K > 256) continue;
+        if (size > 1) {
+            gc::fill(mode, 12345 + left, gc::OP_A, M, K, hA.data());
+            gc::fill(mode, 12345 + left, gc::OP_B, N, K, hBt.data());
+            gc::reference(hA.data(), hBt.data(), M, N, K, ref_left);
         }
+        gc::fill(mode, 12345 + rank, gc::OP_A, M, K, hA.data());
+        gc::fill(mode, 12345 + rank, gc::OP_B, N, K, hBt.data());
+        gc::reference(hA.data(), hBt.data(), M, N, K, ref);
+        HIP(hipMemcpy(A, hA.data(), an * sizeof(uint16_t),
+                      hipMemcpyHostToDevice));
+#if MPIX_GEMM_VARIANT >= 4
+        /* the kernel takes B pre-transposed [N][K], as generated */
+        HIP(hipMemcpy(B, hBt.data(), bn * sizeof(uint16_t),
+                      hipMemcpyHostToDevice));
+#else
+        hB.resize(bn);
+        for (int n = 0; n < N; n++)
+            for (int k = 0; k < K; k++)
+                hB[(size_t)k * N + n] = hBt[(size_t)n * K + k];
+        HIP(hipMemcpy(B, hB.data(), bn * sizeof(uint16_t),
+                      hipMemcpyHostToDevice));
+#endif
+
+        for (int publish = 0; publish <= 1; publish++) {
+            HIP(hipMemset(C, 0xFF, cn * sizeof(uint16_t)));
+            HIP(hipMemset(Crecv, 0xFF, cn * sizeof(uint16_t)));
+            HIP(hipMemset(band_cnt, 0, nparts * sizeof(uint32_t)));
+            HIP(hipDeviceSynchronize());
+            MPI_Barrier(MPI_COMM_WORLD);
+            if (publish) {
+                MPIX_Request act[2] = {pr, ps};
+                CHECK(MPIX_Startall(2, act) == 0);
+            }
+            hipLaunchKernelGGL(gemm_bf16_pready, dim3(grid),
+                               dim3(GEMM_THREADS), 0, st, A, B, C, M, N, K,
+                               band_cnt, nparts, blocks_per_band,
+                               publish ? dps : nullptr, publish);
+            HIP(hipGetLastError());
+            HIP(hipStreamSynchronize(st));
+            if (publish) {
+                /* the kernel is over: a band whose counter is short now was
+                 * never published, and a wait for it would never return */
+                HIP(hipMemcpy(hcnt.data(), band_cnt,
+                              nparts * sizeof(uint32_t),
+                              hipMemcpyDeviceToHost));
+                for (int b = 0; b < nparts; b++)
+                    if (hcnt[b] != (uint32_t)blocks_per_band) {
+                        printf("{\"check\": \"gemm_pready\", \"variant\": "
+                               "%d, \"rank\": %d, \"pass\": \"B\", \"mode\": "
+                               "\"%s\", \"mnk\": [%d, %d, %d], \"nparts\": "
+                               "%d, \"bands_ok\": false, \"ok\": false}\n",
+                               MPIX_GEMM_VARIANT, rank, gc::mode_name(mode),
+                               M, N, K, nparts);
+                        fflush(stdout);
+                        fprintf(stderr, "[r%d] band_cnt[%d] = %u after the "
+                                "kernel, want %d: band not published, not "
+                                "waiting for it\n", rank, b, hcnt[b],
+                                blocks_per_band);
+                        MPI_Abort(MPI_COMM_WORLD, 1);
+                    }
+                CHECK(MPIX_Wait(&pr, MPI_STATUS_IGNORE) == 0);
+                CHECK(MPIX_Wait(&ps, MPI_STATUS_IGNORE) == 0);
+            }
+            HIP(hipMemcpy(hC.data(), Call, hC.size() * sizeof(uint16_t),
+                          hipMemcpyDeviceToHost));
+            HIP(hipMemcpy(hR.data(), Rall, hR.size() * sizeof(uint16_t),
+                          hipMemcpyDeviceToHost));
+            HIP(hipMemcpy(hcnt.data(), band_cnt, nparts * sizeof(uint32_t),
+                          hipMemcpyDeviceToHost));
+            const uint16_t *c = hC.data() + gcn, *r = hR.data() + gcn;
+
+            gc::Result res = gc::compare(mode, c, ref), res_recv;
+            bool guards = all_equal(hC.data(), gcn, SENTINEL) &&
+                          all_equal(c + cn, gcn, SENTINEL) &&
+                          all_equal(hR.data(), gcn, SENTINEL) &&
+                          all_equal(r + cn, gcn, SENTINEL);
+            bool bands = true, identical = true;
+            for (int b = 0; b < nparts; b++)
+                bands = bands &&
+                        hcnt[b] == (publish ? (uint32_t)blocks_per_band : 0u);
+            if (publish) {
+                /* the sender's C, byte for byte */
+                const uint16_t *sent = c;
+                if (size > 1) {
+                    MPI_Sendrecv(c, (int)cn, MPI_UINT16_T, right, 78,
+                                 leftC.data(), (int)cn, MPI_UINT16_T, left,
+                                 78, MPI_COMM_WORLD, MPI_STATUS_IGNORE);
+                    sent = leftC.data();
+                }
+                identical = memcmp(r, sent, cn * sizeof(uint16_t)) == 0;
+                res_recv = gc::compare(mode, r, size > 1 ? ref_left : ref);
+            } else {
+                /* nothing was sent: Crecv is still all poison */
+                identical = all_equal(r, cn, gc::BF16_POISON);
+            }
+            bool ok = res.ok() && res_recv.ok() && guards && bands &&
+                      identical;
+            if (!ok) failed++;
+            char first[64] = "null", first_recv[64] = "null";
+            if (res.bad)
+                snprintf(first, sizeof first, "[%ld, %ld]", res.first_row,
+                         res.first_col);
+            if (res_recv.bad)
+                snprintf(first_recv, sizeof first_recv, "[%ld, %ld]",
+                         res_recv.first_row, res_recv.first_col);
+            printf("{\"check\": \"gemm_pready\", \"variant\": %d, "
+                   "\"rank\": %d, \"ranks\": %d, \"pass\": \"%s\", "
+                   "\"mode\": \"%s\", \"mnk\": [%d, %d, %d], \"nparts\": %d, "
+                   "\"grid\": %d, \"refused\": %s, \"bad\": %zu, "
+                   "\"worst\": %.6g, \"first_bad\": %s, \"recv_bad\": %zu, "
+                   "\"recv_worst\": %.6g, \"recv_first_bad\": %s, "
+                   "\"recv_identical\": %s, \"bands_ok\": %s, "
+                   "\"guards_ok\": %s, \"ok\": %s}\n",
+                   MPIX_GEMM_VARIANT, rank, size, publish ? "B" : "A",
+                   gc::mode_name(mode), M, N, K, nparts, grid,
+                   res.refused || res_recv.refused ? "true" : "false",
+                   res.bad, gc::json_num(res.worst), first, res_recv.bad,
+                   gc::json_num(res_recv.worst), first_recv,
+                   identical ? "true" : "false", bands ? "true" : "false",
+                   guards ? "true" : "false", ok ? "true" : "false");
+            fflush(stdout);
+            if (res.bad)
+                fprintf(stderr, "[r%d] pass %s %s: first bad of C: %s\n",
+                        rank, publish ? "B" : "A", gc::mode_name(mode),
+                        gc::address(res).c_str());
+            if (res_recv.bad)
+                fprintf(stderr, "[r%d] pass %s %s: first bad of Crecv: %s\n",
+                        rank, publish ? "B" : "A", gc::mode_name(mode),
+                        gc::address(res_recv).c_str());
+            if (!bands)
+                for (int b = 0; b < nparts; b++)
+                    fprintf(stderr, "[r%d] band_cnt[%d] = %u, want %d\n",
+                            rank, b, hcnt[b],
+                            publish ? blocks_per_band : 0);
+        }
+    }
+
+    CHECK(MPIX_Prequest_free(&dps) == 0);
+    CHECK(MPIX_Request_free(&ps) == 0);
+    CHECK(MPIX_Request_free(&pr) == 0);
+    (void)hipFree(Aall); (void)hipFree(Ball); (void)hipFree(Call);
+    (void)hipFree(Rall); (void)hipFree(band_cnt);
+    (void)hipStreamDestroy(st);
+    printf("[r%d] gemm --check M=%d N=%d K=%d nparts=%d -> %s\n", rank, M, N,
+           K, nparts, failed ? "FAIL" : "PASS");
+    return failed;
 }
 
 int main(int argc, char **argv)
@@ -912,12 +1133,35 @@ int main(int argc, char **argv)
     MPI_Comm_rank(MPI_COMM_WORLD, &rank);
     MPI_Comm_size(MPI_COMM_WORLD, &size);
 
+    /* --check [M N K [nparts]]; bare --check is 256 256 512, one band per
+     * tile row */
     bool check = argc > 1 && strcmp(argv[1], "--check") == 0;
+    bool shaped = check && argc > 4;
     int M = check ? 256 : (argc > 1 ? atoi(argv[1]) : 8192);
     int N = check ? 256 : (argc > 2 ? atoi(argv[2]) : 8192);
     int K = check ? 512 : (argc > 3 ? atoi(argv[3]) : 8192);
+    if (shaped) {
+        M = atoi(argv[2]);
+        N = atoi(argv[3]);
+        K = atoi(argv[4]);
+    }
     int iters = check ? 1 : (argc > 4 ? atoi(argv[4]) : 10);
     int warmup = check ? 0 : 3;
+
+    /* the shape is judged before anything touches the device */
+    CHECK(M > 0 && N > 0 && K > 0);
+    CHECK(M % BM == 0 && N % BN == 0 && K % BK == 0);
+    /* one band >= one tile row; clamp so small M still works */
+    int nparts = check ? (argc > 5 ? atoi(argv[5]) : M / BM)
+                       : (M / BM < NPARTS ? M / BM : NPARTS);
+#if MPIX_GEMM_VARIANT == 6
+    /* 8-phase pair schedule: K-tiles are computed in pairs, and the
+     * prologue has six pieces of tiles 0 and 1 in flight for a first
+     * iteration that is followed by another */
+    CHECK(K % (2 * BK) == 0 && K >= 4 * BK);
+#endif
+    CHECK(nparts >= 1 && M % nparts == 0 && (M / nparts) % BM == 0);
+    int blocks_per_band = (M / nparts / BM) * (N / BN);
 
     int ndev = 0;
     HIP(hipGetDeviceCount(&ndev));
@@ -926,14 +1170,12 @@ int main(int argc, char **argv)
     CHECK(MPIX_Init() == 0);
     int right = (rank + 1) % size, left = (rank - 1 + size) % size;
 
-    CHECK(M % BM == 0 && N % BN == 0 && K % BK == 0);
-    /* one band >= one tile row; clamp so small M still works */
-    int nparts = check ? M / BM : (M / BM < NPARTS ? M / BM : NPARTS);
-#if MPIX_GEMM_VARIANT == 6
-    CHECK(K % (2 * BK) == 0 && K >= 4 * BK); /* 8-phase pair schedule */
-#endif
-    CHECK(M % nparts == 0 && (M / nparts) % BM == 0);
-    int blocks_per_band = (M / nparts / BM) * (N / BN);
+    if (check) {
+        int failed = run_check(rank, size, M, N, K, nparts);
+        MPIX_Finalize();
+        MPI_Finalize();
+        return failed ? 1 : 0;
+    }
 
     size_t an = (size_t)M * K, bn = (size_t)K * N, cn = (size_t)M * N;
     bf16 *A, *B, *C, *Crecv;
@@ -965,43 +1207,6 @@ int main(int argc, char **argv)
     hipStream_t st;
     HIP(hipStreamCreate(&st));
     int grid = (M / BM) * (N / BN);
-
-    if (check) {
-        HIP(hipMemset(band_cnt, 0, nparts * sizeof(uint32_t)));
-        hipLaunchKernelGGL(gemm_bf16_pready, dim3(grid), dim3(GEMM_THREADS), 0, st,
-                           A, B, C, M, N, K, band_cnt, nparts, blocks_per_band,
-                           nullptr, 0);
-        HIP(hipStreamSynchronize(st));
-        std::vector<bf16> hA(an), hB(bn), hC(cn);
-        HIP(hipMemcpy(hA.data(), A, an * sizeof(bf16), hipMemcpyDeviceToHost));
-        HIP(hipMemcpy(hB.data(), B, bn * sizeof(bf16), hipMemcpyDeviceToHost));
-        HIP(hipMemcpy(hC.data(), C, cn * sizeof(bf16), hipMemcpyDeviceToHost));
-        std::vector<float> fA(an), fB(bn), fC(cn);
-        for (size_t i = 0; i < an; i++) fA[i] = (float)hA[i];
-#if MPIX_GEMM_VARIANT >= 4
-        /* kernel takes B pre-transposed [N][K]; reference wants [K][N] */
-        for (int k = 0; k < K; k++)
-            for (int n = 0; n < N; n++)
-                fB[(size_t)k * N + n] = (float)hB[(size_t)n * K + k];
-#else
-        for (size_t i = 0; i < bn; i++) fB[i] = (float)hB[i];
-#endif
-        host_gemm_ref(fA, fB, fC, M, N, K);
-        int bad = 0;
-        float worst = 0.f;
-        for (size_t i = 0; i < cn; i++) {
-            float got = (float)hC[i], want = fC[i];
-            float err = fabsf(got - want) / (fabsf(want) + 1.f);
-            if (err > worst) worst = err;
-            if (err > 0.05f) bad++;
-        }
-        printf("[r%d] gemm --check M=%d N=%d K=%d: %d/%zu bad, worst relerr "
-               "%.4f -> %s\n", rank, M, N, K, bad, cn, worst,
-               bad ? "FAIL" : "PASS");
-        MPIX_Finalize();
-        MPI_Finalize();
-        return bad ? 1 : 0;
-    }
 
     MPIX_Request ps, pr;
     int count = (int)(cn / nparts);
