@@ -711,9 +711,10 @@ extern "C" int MPIX_Finalize(void)
                     s->settle ? "on" : "off");
         if (s->word_event_n)
             fprintf(stderr,
-                    "[mpix stats r%d] MPIX_PULL_DONE=word: completion word "
+                    "[mpix stats r%d] MPIX_PULL_DONE=%s: completion word "
                     "seen -> event seen, mean us over %lu batches: %.1f\n",
-                    s->world_rank, (unsigned long)s->word_event_n,
+                    s->world_rank, s->pull_done_name,
+                    (unsigned long)s->word_event_n,
                     (double)s->word_event_ns / 1e3 / (double)s->word_event_n);
         if (s->compl_groups)
             fprintf(stderr,

@@ -406,9 +406,11 @@ struct State {
     std::atomic<uint64_t> start_ns{0}, start_max_ns{0}, start_n{0};
     std::atomic<uint64_t> reset_ns{0}, reset_max_ns{0}, reset_n{0};
     std::atomic<uint64_t> arm_pushes{0};
-    /* MPIX_PULL_DONE=word: batches whose word was seen, and for them the
-     * time until the event recorded behind the same kernel was seen too */
+    /* MPIX_PULL_DONE=word, tail: batches whose word was seen, and
+     * for them the time until the event recorded behind the same kernel(s)
+     * was seen too; the mode's name as it was given */
     uint64_t word_event_ns = 0, word_event_n = 0;
+    char pull_done_name[16] = "";
     bool settle = true;             /* MPIX_SETTLE, see proxy.cpp */
     bool bleg_first_seen = false;
     uint64_t bleg_first_wait_ns = 0, bleg_first_call_ns = 0;

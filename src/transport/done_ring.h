@@ -1,12 +1,14 @@
 /* mpix — completion words of the batched pull: host-side bookkeeping (no HIP
  * dependency, checked on its own by tests/native/done_ring_check.cpp).
  *
- * With MPIX_PULL_DONE=word a pull kernel tells the proxy that it has finished
- * by storing a sequence number into a 64-bit word in pinned host memory (the
- * kernel side is pull_signal_done in pull_kernels.h) instead of through an event
- * recorded behind the launch.  The words form a small ring of
- * MPIX_DONE_SLOTS; each slot also owns a 32-bit arrival counter in device
- * memory, which the kernel's last block leaves at 0 again.
+ * With MPIX_PULL_DONE=word a pull kernel tells the proxy that it
+ * has finished by storing a sequence number into a 64-bit word in pinned host
+ * memory (the kernel side is pull_signal_done in pull_kernels.h) instead of
+ * through an event recorded behind the launch; with MPIX_PULL_DONE=tail a
+ * one-thread kernel behind the copy stores it (k_pull_tail).  The words form
+ * a small ring of MPIX_DONE_SLOTS; each slot also owns a 32-bit arrival
+ * counter in device memory, which the arrival of the kernel's last block
+ * leaves at 0 again (tail does not use it).
  *
  * A batch ACQUIRES a slot and with it a fresh sequence number, hands both to
  * the kernel, tests the word with done_seen(), and RELEASES the slot once

@@ -97,18 +97,31 @@ static bool part_runs_on()
     return v;
 }
 
-/* MPIX_PULL_DONE=word|event: how a pull kernel's completion reaches the
- * proxy.  event (default): an event recorded behind the launch and tested
- * with hipEventQuery in every pass.  word: the kernel's last block stores a
- * sequence number to pinned host memory (done_ring.h, pull_signal_done); no
- * event, no runtime call per pass.  A/B: profiles/batch_handoffs.md. */
-static bool pull_done_word()
+/* MPIX_PULL_DONE=word|tail|event: how a pull batch's completion reaches
+ * the proxy.
+ *  word   (default) the copy kernel stores its payload write-through (sc1)
+ *         and its last block stores a sequence number to pinned host memory
+ *         (done_ring.h, pull_signal_done); no event, no runtime call per
+ *         pass.  hipMemcpyAsync pulls complete by event.
+ *  tail   the event path's kernel (or the hipMemcpyAsync), and a one-thread
+ *         kernel behind it on the stream that stores the sequence number.
+ *  event  an event recorded behind the launch and tested with hipEventQuery
+ *         in every pass.
+ * None of them waits on the device.  A/B: profiles/pull_done_modes.md. */
+enum class PullDoneMode { EVENT, WORD, TAIL };
+static const char *const PULL_DONE_DEFAULT = "word";
+
+static PullDoneMode pull_done_mode()
 {
-    static const bool v = [] {
+    static const PullDoneMode v = [] {
         const char *e = getenv("MPIX_PULL_DONE");
-        if (e != nullptr && strcmp(e, "word") != 0 && strcmp(e, "event") != 0)
-            MPIX_ERR("MPIX_PULL_DONE=%s is neither word nor event: event", e);
-        return e != nullptr && strcmp(e, "word") == 0;
+        if (e == nullptr) e = PULL_DONE_DEFAULT;
+        if (strcmp(e, "word") == 0) return PullDoneMode::WORD;
+        if (strcmp(e, "tail") == 0) return PullDoneMode::TAIL;
+        if (strcmp(e, "event") != 0)
+            MPIX_ERR("MPIX_PULL_DONE=%s is none of word, tail, event: event",
+                     e);
+        return PullDoneMode::EVENT;
     }();
     return v;
 }
@@ -119,7 +132,9 @@ static bool pull_done_word()
  * earlier kernel.  MPIX_PULL_NT=0 turns the nontemporal loads and stores
  * off: the payload is touched once and is far larger than L2, and keeping
  * it out of the caches is where the gain over the earlier kernel comes
- * from (with plain accesses the tiled kernel is slower than that one).
+ * from (with plain accesses the tiled kernel is slower than that one); it
+ * applies to the kernels of MPIX_PULL_DONE=event and tail, the word kernels
+ * always load nontemporal and store write-through.
  * MPIX_PULL_BLOCKS caps the blocks of a launch (A/B in the same profile). */
 static int pull_unroll()
 {
@@ -264,29 +279,30 @@ private:
     std::vector<PendingPull> pend_pulls_;
     /* what is in flight on a copy stream, in submission order */
     struct PullBatch {
-        hipEvent_t ev = nullptr; /* event path; word path: only MPIX_STATS=1 */
-        int done_slot = -1;   /* word path: slot of done_ring_, else -1 */
+        hipEvent_t ev = nullptr; /* event path; word paths: only MPIX_STATS=1 */
+        int done_slot = -1;   /* word paths: slot of done_ring_, else -1 */
         hipStream_t cs = nullptr;
-        uint64_t t_born_ns = 0;  /* word path: for the lost-signal guard */
-        uint32_t passes = 0;     /* word path: passes that found no word */
+        uint64_t t_born_ns = 0;  /* word paths: for the lost-signal guard */
+        uint32_t passes = 0;     /* word paths: passes that found no word */
         uint64_t t_launch_ns = 0; /* MPIX_STATS=1, contiguous kernel batches */
         bool first = false;   /* MPIX_STATS=1: first batch of the process */
         bool memcpy_pull = false; /* hipMemcpyAsync, not a kernel */
         std::vector<PendingPull> items;
     };
     std::list<PullBatch> batches_;
-    /* MPIX_PULL_DONE=word: completion words in pinned host memory, one per
-     * 64 bytes, and arrival counters in device memory, one per 128 bytes
-     * (done_ring.h has the bookkeeping) */
+    /* MPIX_PULL_DONE=word, tail (the word paths): completion words
+     * in pinned host memory, one per 64 bytes, and arrival counters in
+     * device memory, one per 128 bytes, which tail leaves alone (done_ring.h
+     * has the bookkeeping) */
     static constexpr size_t DONE_WORD_STRIDE = 8;     /* in uint64_t */
     static constexpr size_t DONE_COUNTER_STRIDE = 32; /* in uint32_t */
-    bool done_word_ = false;
+    PullDoneMode done_mode_ = PullDoneMode::EVENT; /* EVENT: no words */
     DoneRing done_ring_;
     std::atomic<uint64_t> *done_words_ = nullptr; /* host view */
     uint64_t *done_words_d_ = nullptr;            /* device view */
     uint32_t *done_counters_ = nullptr;
-    /* MPIX_STATS=1 with word: the event recorded all the same, kept after
-     * the word was seen to measure word seen -> event seen */
+    /* MPIX_STATS=1 on a word path: the event recorded all the same, kept
+     * after the word was seen to measure word seen -> event seen */
     struct WordEvent {
         hipEvent_t ev;
         uint64_t t_word_ns;
@@ -295,6 +311,8 @@ private:
     bool batch_done(PullBatch &b, hipError_t *err);
     PullBatch &push_batch(std::vector<PendingPull> items, hipStream_t cs,
                           int slot);
+    int acquire_done(PullDone *done);
+    int signal_by_tail(int slot, const PullDone &done, hipStream_t cs);
     template <typename Launch>
     PullBatch *submit_batch(std::vector<PendingPull> items, hipStream_t cs,
                             const char *kernel, Launch launch);
@@ -516,7 +534,7 @@ int NativeTransport::init()
             MPIX_ERR("copy stream create failed");
             return -1;
         }
-        if (pull_done_word()) {
+        if (pull_done_mode() != PullDoneMode::EVENT) {
             void *w = nullptr, *wd = nullptr, *c = nullptr;
             const size_t wbytes =
                 MPIX_DONE_SLOTS * DONE_WORD_STRIDE * sizeof(uint64_t);
@@ -526,14 +544,20 @@ int NativeTransport::init()
                 hipHostGetDevicePointer(&wd, w, 0) != hipSuccess ||
                 hipMalloc(&c, cbytes) != hipSuccess ||
                 hipMemset(c, 0, cbytes) != hipSuccess) {
-                MPIX_ERR("MPIX_PULL_DONE=word: completion words not allocated");
+                MPIX_ERR("MPIX_PULL_DONE: completion words not allocated");
                 return -1;
             }
             memset(w, 0, wbytes);
             done_words_ = reinterpret_cast<std::atomic<uint64_t> *>(w);
             done_words_d_ = (uint64_t *)wd;
             done_counters_ = (uint32_t *)c;
-            done_word_ = true;
+            done_mode_ = pull_done_mode();
+            if (g_state != nullptr) {
+                const char *e = getenv("MPIX_PULL_DONE");
+                snprintf(g_state->pull_done_name,
+                         sizeof(g_state->pull_done_name), "%s",
+                         e ? e : PULL_DONE_DEFAULT);
+            }
         }
         /* the standing priority stream, for experiments only */
         if (env_flag("MPIX_COPY_PRIO_STREAM")) copy_big_ = prio_stream();
@@ -558,7 +582,7 @@ void NativeTransport::shutdown()
     done_words_ = nullptr;
     done_words_d_ = nullptr;
     done_counters_ = nullptr;
-    done_word_ = false;
+    done_mode_ = PullDoneMode::EVENT;
     for (hipStream_t *s : {&copy_stream_, &copy_big_, &copy_retired_}) {
         if (*s) (void)hipStreamDestroy(*s);
         *s = nullptr;
@@ -1175,8 +1199,9 @@ void NativeTransport::start_dev_copy(InboundMsg &m)
         erase_inbound(&m);
         return;
     }
-    /* a batch of one, always on the event path: a runtime copy cannot store
-     * a completion word.  t_launch_ns stays 0 */
+    /* a batch of one.  A runtime copy cannot store a completion word, so it
+     * completes by event, or by the tail kernel behind it in that mode.
+     * t_launch_ns stays 0 */
     hipStream_t cs = copy_stream(n);
     hipError_t e = hipSuccess;
     if (n > 0) e = hipMemcpyAsync(op->buf, src, n, hipMemcpyDefault, cs);
@@ -1190,7 +1215,12 @@ void NativeTransport::start_dev_copy(InboundMsg &m)
     if (trace_on())
         fprintf(stderr, "[mpix trace] pull start %lu B via memcpyAsync "
                 "(dst=%p src=%p)\n", (unsigned long)n, op->buf, src);
-    push_batch({pp}, cs, -1).memcpy_pull = true;
+    int slot = -1;
+    if (done_mode_ == PullDoneMode::TAIL) {
+        PullDone done{nullptr, nullptr, 0};
+        slot = signal_by_tail(acquire_done(&done), done, cs);
+    }
+    push_batch({pp}, cs, slot).memcpy_pull = true;
     erase_inbound(&m);
 }
 
@@ -1215,25 +1245,49 @@ NativeTransport::PullBatch &NativeTransport::push_batch(
     return b;
 }
 
+/* A slot of the ring and the kernel argument for it, on a word path; -1:
+ * the event path (MPIX_PULL_DONE=event, or the ring is full). */
+int NativeTransport::acquire_done(PullDone *done)
+{
+    if (done_mode_ == PullDoneMode::EVENT) return -1;
+    const int slot = done_acquire(&done_ring_, &done->seq);
+    if (slot >= 0) {
+        done->counter = done_counters_ + (size_t)slot * DONE_COUNTER_STRIDE;
+        done->word = done_words_d_ + (size_t)slot * DONE_WORD_STRIDE;
+    }
+    return slot;
+}
+
+/* Tail mode: the kernel that stores the word of `slot`, behind what was just
+ * put on `cs`.  Returns the slot; or -1 (the slot was -1, or the launch
+ * failed and the slot was given back): the copy is on the stream all the
+ * same, and its batch completes by event. */
+int NativeTransport::signal_by_tail(int slot, const PullDone &done,
+                                    hipStream_t cs)
+{
+    if (slot < 0) return -1;
+    launch_tail(done.word, done.seq, cs);
+    if (hipGetLastError() == hipSuccess) return slot;
+    done_release(&done_ring_, slot);
+    return -1;
+}
+
 /* The second half of a flush: `items` go out as one launch on `cs`.
  * launch(done) issues the kernel (done: the argument of the completion
- * word, or nullptr on the event path) and returns the launch's error.
- * Returns the batch; or nullptr: the launch failed, and every item was
- * finished with MPI_ERR_OTHER. */
+ * word, or nullptr for the kernel that signals nothing) and returns the
+ * launch's error.  In tail mode the signal is a launch of its own behind
+ * that kernel.  Returns the batch; or nullptr: the launch failed, and every
+ * item was finished with MPI_ERR_OTHER. */
 template <typename Launch>
 NativeTransport::PullBatch *NativeTransport::submit_batch(
     std::vector<PendingPull> items, hipStream_t cs, const char *kernel,
     Launch launch)
 {
-    /* word path: a slot and the kernel's argument for it; event path
-     * (MPIX_PULL_DONE=event, or the ring is full): slot -1 */
     PullDone done{nullptr, nullptr, 0};
-    const int slot = done_word_ ? done_acquire(&done_ring_, &done.seq) : -1;
-    if (slot >= 0) {
-        done.counter = done_counters_ + (size_t)slot * DONE_COUNTER_STRIDE;
-        done.word = done_words_d_ + (size_t)slot * DONE_WORD_STRIDE;
-    }
-    const hipError_t e = launch(slot >= 0 ? &done : nullptr);
+    int slot = acquire_done(&done);
+    const bool tail = done_mode_ == PullDoneMode::TAIL;
+    const hipError_t e = launch(slot >= 0 && !tail ? &done : nullptr);
+    if (e == hipSuccess && tail) slot = signal_by_tail(slot, done, cs);
     if (e != hipSuccess) {
         MPIX_ERR("%s launch failed: %s", kernel, hipGetErrorString(e));
         if (slot >= 0) done_release(&done_ring_, slot);
@@ -1354,8 +1408,9 @@ void NativeTransport::flush_strided()
 }
 
 /* Is the batch's work finished?  *err: hipSuccess, or why its ops fail.
- * Event path: hipEventQuery.  Word path: a plain acquire load of the slot's
- * host word, no runtime call.  A kernel that dies never stores its word, so
+ * Event path: hipEventQuery.  Word paths (the tail kernel's word too): a
+ * plain acquire load of the slot's host word, no runtime call.  A kernel
+ * that dies never stores its word, nor does one behind it on the stream, so
  * for a batch older than a second the stream is asked, once per 4096 passes
  * that found no word: an error there fails the batch (reasoned, not
  * exercised: nothing in the tests makes a kernel fail). */

@@ -28,42 +28,99 @@ namespace mpix {
  * and its n % 16 tail bytes take the slow branch.  No spin-wait in here, in
  * either variant (see maybe_switch_prio for why nothing may park on a
  * queue).  k_pull_multi carries no completion signal: its completion is the
- * event recorded behind the launch.  k_pull_multi_done (MPIX_PULL_DONE=word)
- * is the same copy followed by pull_signal_done, which nothing waits for
- * on the device either. */
+ * event recorded behind the launch, or k_pull_tail behind it on the stream
+ * (MPIX_PULL_DONE=tail).  k_pull_multi_done (MPIX_PULL_DONE=word) is the
+ * same copy with every payload store written through, followed by
+ * pull_signal_done, which nothing waits for on the device either. */
 #define PULL_THREADS 256
 typedef unsigned int pull_v4 __attribute__((ext_vector_type(4)));
 typedef const __attribute__((address_space(1))) pull_v4 *pull_gsrc;
 typedef __attribute__((address_space(1))) pull_v4 *pull_gdst;
 
-template <bool NT>
-static __device__ __forceinline__ pull_v4 pull_ld(pull_gsrc p)
+/* How a kernel stores the payload (its loads are nontemporal unless the
+ * policy is PULL_ST_PLAIN):
+ *   PULL_ST_NT     nontemporal stores: the event and tail kernels.  The lines
+ *                  stay dirty in the L2 of the block's XCD until the end of
+ *                  the kernel writes them back.
+ *   PULL_ST_PLAIN  cached loads and stores (MPIX_PULL_NT=0).
+ *   PULL_ST_WT     write-through stores (sc1): the bytes are in memory once
+ *                  the storing wave's vmcnt has drained, so the completion
+ *                  word needs no release fence (pull_signal_done).  It
+ *                  covers EVERY payload store of the kernel: the partial
+ *                  last tile and the n % 16 tail bytes too.  (sc1 nt was
+ *                  measured and lost: profiles/pull_done_modes.md.)
+ */
+enum PullStore { PULL_ST_NT, PULL_ST_PLAIN, PULL_ST_WT };
+
+static constexpr bool pull_write_through(PullStore S)
 {
-    return NT ? __builtin_nontemporal_load(p) : *p;
+    return S == PULL_ST_WT;
 }
 
-template <bool NT>
+template <PullStore S>
+static __device__ __forceinline__ pull_v4 pull_ld(pull_gsrc p)
+{
+    return S != PULL_ST_PLAIN ? __builtin_nontemporal_load(p) : *p;
+}
+
+/* The 16-byte store of a full tile.  The write-through form is written
+ * as asm: the compiler has no 16-byte atomic store to lower to it.  The
+ * s_nop covers the wait states between a store of more than 64 bits and an
+ * overwrite of its data registers, which the compiler does not count for
+ * asm. */
+template <PullStore S>
 static __device__ __forceinline__ void pull_st(pull_gdst p, pull_v4 v)
 {
-    if (NT)
+    if (S == PULL_ST_WT)
+        asm volatile("global_store_dwordx4 %0, %1, off sc1\n\ts_nop 1"
+                     :: "v"(p), "v"(v) : "memory");
+    else if (S == PULL_ST_NT)
         __builtin_nontemporal_store(v, p);
     else
         *p = v;
 }
 
-/* Completion word (done_ring.h), device side.  Every block arrives at the
- * slot's counter once its own stores are out of the XCD's L2; the block
- * whose add is the last of the grid zeroes the counter for the slot's next
- * user and publishes the sequence number to the host word.  Nothing waits
- * and nothing spins.
- *  - each wave drains its own stores (vmcnt counts stores on gfx9), then the
- *    block barrier: thread 0 signals for all waves of the block;
- *  - agent-scope release before the add: nontemporal stores stay in the L2
- *    of the XCD, and the host word must not overtake them.  The wait behind
- *    the fence is written as asm so that it cannot be dropped;
- *  - the last arriver's add returned gridDim.x - 1, so every other block's
- *    release happened before it; its system-scope release store orders the
- *    counter reset and the word behind all of that. */
+/* Stores of the slow branches (partial tiles, tail bytes, the element path
+ * of the strided kernel): T is 16, 8, 4, 2 or 1 bytes.  Write-through: the
+ * 16-byte form above, and a relaxed agent-scope atomic store below that,
+ * which is the same store with sc1.  Otherwise NT says which. */
+template <PullStore S, typename T, bool NT>
+static __device__ __forceinline__ void pull_st_any(
+    __attribute__((address_space(1))) T *p, T v)
+{
+    if constexpr (pull_write_through(S)) {
+        if constexpr (sizeof(T) == 16)
+            pull_st<S>((pull_gdst)p, v);
+        else
+            __hip_atomic_store(p, v, __ATOMIC_RELAXED,
+                               __HIP_MEMORY_SCOPE_AGENT);
+    } else {
+        if constexpr (NT)
+            __builtin_nontemporal_store(v, p);
+        else
+            *p = v;
+    }
+}
+
+/* Completion word (done_ring.h), device side, for kernels whose payload
+ * stores are all write-through.  Every block arrives at the slot's counter
+ * once its own stores are in memory; the block whose arrival is the last of
+ * the grid publishes the sequence number to the host word.  Nothing waits
+ * and nothing spins, and there is no fence: a release at agent scope is a
+ * write-back of the XCD's whole L2 (buffer_wbl2), and 1024 of them at the
+ * end of a 256 MiB copy cost 50 us (profiles/batch_handoffs.md section 5).
+ *  - each wave drains its own stores (vmcnt counts stores on gfx9; written
+ *    as asm so that it cannot be dropped or moved), then the block barrier:
+ *    thread 0 signals for all waves of the block;
+ *  - the arrival is an atomic increment that wraps at gridDim.x - 1
+ *    (relaxed, agent scope): the last arriver's own atomic leaves the
+ *    counter at 0 for the slot's next user, so there is no reset store that
+ *    the word could overtake;
+ *  - why that is enough: every payload byte was written through and its
+ *    store acknowledged before its block's increment was issued, and the
+ *    increment that returned gridDim.x - 1 came after all the others.  The
+ *    word is a relaxed system-scope store; a release there would bring one
+ *    buffer_wbl2 back. */
 struct PullDone {
     uint32_t *counter; /* device memory, 0 between uses */
     uint64_t *word;    /* pinned host memory */
@@ -75,21 +132,22 @@ static __device__ __forceinline__ void pull_signal_done(const PullDone &d)
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     __syncthreads();
     if (threadIdx.x == 0) {
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        const uint32_t before = __hip_atomic_fetch_add(
-            d.counter, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        if (before == gridDim.x - 1) {
-            __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
-            __hip_atomic_store(d.counter, 0u, __ATOMIC_RELAXED,
-                               __HIP_MEMORY_SCOPE_AGENT);
-            __hip_atomic_store(d.word, d.seq, __ATOMIC_RELEASE,
+        const uint32_t before = atomicInc(d.counter, gridDim.x - 1);
+        if (before == gridDim.x - 1)
+            __hip_atomic_store(d.word, d.seq, __ATOMIC_RELAXED,
                                __HIP_MEMORY_SCOPE_SYSTEM);
-        }
     }
 }
 
-template <int U, bool NT>
+/* MPIX_PULL_DONE=tail: one thread, launched on the copy's stream straight
+ * behind the copy kernel or the hipMemcpyAsync.  Ordering and visibility are
+ * those of two kernels on one stream. */
+__global__ void k_pull_tail(uint64_t *word, uint64_t seq)
+{
+    __hip_atomic_store(word, seq, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+}
+
+template <int U, PullStore S>
 static __device__ __forceinline__ void pull_multi_body(const PullTable &t)
 {
     constexpr uint64_t TILE = (uint64_t)PULL_THREADS * U * 16;
@@ -115,34 +173,41 @@ static __device__ __forceinline__ void pull_multi_body(const PullTable &t)
             pull_v4 r[U];
 #pragma unroll
             for (int k = 0; k < U; k++)
-                r[k] = pull_ld<NT>(s + threadIdx.x + k * PULL_THREADS);
+                r[k] = pull_ld<S>(s + threadIdx.x + k * PULL_THREADS);
 #pragma unroll
             for (int k = 0; k < U; k++)
-                pull_st<NT>(d + threadIdx.x + k * PULL_THREADS, r[k]);
+                pull_st<S>(d + threadIdx.x + k * PULL_THREADS, r[k]);
         } else {
+            typedef __attribute__((address_space(1))) char *gchar;
             const uint32_t nv = (uint32_t)(left / 16);
-            for (uint32_t v = threadIdx.x; v < nv; v += PULL_THREADS)
-                d[v] = s[v];
+            for (uint32_t v = threadIdx.x; v < nv; v += PULL_THREADS) {
+                if constexpr (pull_write_through(S))
+                    pull_st<S>(d + v, s[v]);
+                else
+                    d[v] = s[v];
+            }
             if (threadIdx.x < (uint32_t)(left & 15)) {
                 const uint64_t b = (uint64_t)nv * 16 + threadIdx.x;
-                ((__attribute__((address_space(1))) char *)d)[b] =
-                    ((const __attribute__((address_space(1))) char *)s)[b];
+                pull_st_any<S, char, false>(
+                    (gchar)d + b,
+                    ((const __attribute__((address_space(1))) char *)s)[b]);
             }
         }
     }
 }
 
-template <int U, bool NT>
+template <int U, PullStore S>
 __global__ __launch_bounds__(PULL_THREADS) void k_pull_multi(const PullTable t)
 {
-    pull_multi_body<U, NT>(t);
+    pull_multi_body<U, S>(t);
 }
 
-template <int U, bool NT>
+template <int U, PullStore S>
 __global__ __launch_bounds__(PULL_THREADS) void k_pull_multi_done(
     const PullTable t, const PullDone d)
 {
-    pull_multi_body<U, NT>(t);
+    static_assert(pull_write_through(S), "the word needs write-through stores");
+    pull_multi_body<U, S>(t);
     pull_signal_done(d);
 }
 
@@ -167,8 +232,10 @@ __global__ __launch_bounds__(PULL_THREADS) void k_pull_multi_done(
  * number, shared by both sides since partitions have one size.  It is right
  * for every entry (one without a partition level has a quotient of 0), and
  * launched only when a batch holds a run entry, so plain strided messages
- * do not pay the third division. */
-template <typename T, int ROUNDS, bool WIDE, bool PARTS>
+ * do not pay the third division.  S is the store policy, as in the
+ * contiguous kernel: nontemporal, or write-through in the kernels that
+ * signal the completion word. */
+template <typename T, int ROUNDS, bool WIDE, bool PARTS, PullStore S>
 static __device__ __forceinline__ void strided_tile(const StridedEntry &e,
                                                     uint64_t unit0)
 {
@@ -196,11 +263,11 @@ static __device__ __forceinline__ void strided_tile(const StridedEntry &e,
 #pragma unroll
         for (int k = 0; k < U; k++)
             if (ok[k])
-                __builtin_nontemporal_store(r[k], (gdst)(e.dst + doff[k]));
+                pull_st_any<S, T, true>((gdst)(e.dst + doff[k]), r[k]);
     }
 }
 
-template <bool WIDE, bool PARTS>
+template <bool WIDE, bool PARTS, PullStore S>
 static __device__ __forceinline__ void pull_strided_body(const StridedTable &t)
 {
     const uint64_t total = t.tile_end[t.n - 1];
@@ -218,11 +285,11 @@ static __device__ __forceinline__ void pull_strided_body(const StridedTable &t)
         /* units of this tile start at (tile bytes) >> glog */
         const uint64_t unit0 = ((tile - first) * MPIX_STRIDED_TILE) >> cur.glog;
         switch (cur.glog) {
-        case 4: strided_tile<pull_v4, 1, WIDE, PARTS>(cur, unit0); break;
-        case 3: strided_tile<uint64_t, 2, WIDE, PARTS>(cur, unit0); break;
-        case 2: strided_tile<uint32_t, 4, WIDE, PARTS>(cur, unit0); break;
-        case 1: strided_tile<uint16_t, 8, WIDE, PARTS>(cur, unit0); break;
-        default: strided_tile<uint8_t, 16, WIDE, PARTS>(cur, unit0); break;
+        case 4: strided_tile<pull_v4, 1, WIDE, PARTS, S>(cur, unit0); break;
+        case 3: strided_tile<uint64_t, 2, WIDE, PARTS, S>(cur, unit0); break;
+        case 2: strided_tile<uint32_t, 4, WIDE, PARTS, S>(cur, unit0); break;
+        case 1: strided_tile<uint16_t, 8, WIDE, PARTS, S>(cur, unit0); break;
+        default: strided_tile<uint8_t, 16, WIDE, PARTS, S>(cur, unit0); break;
         }
     }
 }
@@ -231,45 +298,49 @@ template <bool WIDE, bool PARTS>
 __global__ __launch_bounds__(PULL_THREADS) void k_pull_strided(
     const StridedTable t)
 {
-    pull_strided_body<WIDE, PARTS>(t);
+    pull_strided_body<WIDE, PARTS, PULL_ST_NT>(t);
 }
 
-/* MPIX_PULL_DONE=word: see pull_signal_done */
-template <bool WIDE, bool PARTS>
+/* MPIX_PULL_DONE=word: write-through stores, then pull_signal_done */
+template <bool WIDE, bool PARTS, PullStore S>
 __global__ __launch_bounds__(PULL_THREADS) void k_pull_strided_done(
     const StridedTable t, const PullDone d)
 {
-    pull_strided_body<WIDE, PARTS>(t);
+    static_assert(pull_write_through(S), "the word needs write-through stores");
+    pull_strided_body<WIDE, PARTS, S>(t);
     pull_signal_done(d);
 }
 
-/* Launch dispatch.  Each variant comes as a pair: the kernel that signals
- * the completion word, launched when `done` is given, and the plain one
- * whose completion is an event.  unroll is 1, 8 or (anything else) 4. */
-struct PullKernel { /* of one unroll; [0] nontemporal, [1] cached accesses */
-    void (*by_word[2])(const PullTable, const PullDone);
-    void (*by_event[2])(const PullTable);
+/* Launch dispatch.  Each variant comes as a pair: the kernel that stores
+ * write-through and signals the completion word, launched when `done` is
+ * given, and the plain one whose completion is an event or a tail kernel
+ * (`nt`: its loads and stores nontemporal, or cached).  unroll is 1, 8 or
+ * (anything else) 4. */
+struct PullKernel { /* of one unroll */
+    void (*by_word)(const PullTable, const PullDone);
+    void (*by_event[2])(const PullTable); /* [0] nontemporal, [1] cached */
 };
 struct StridedKernel {
     void (*by_word)(const StridedTable, const PullDone);
     void (*by_event)(const StridedTable);
 };
 
+#define PULL_KERNELS(U)                  \
+    {k_pull_multi_done<U, PULL_ST_WT>,   \
+     {k_pull_multi<U, PULL_ST_NT>, k_pull_multi<U, PULL_ST_PLAIN>}}
+#define STRIDED_KERNELS(W, P) \
+    {k_pull_strided_done<W, P, PULL_ST_WT>, k_pull_strided<W, P>}
+
 static inline void launch_pull(const PullTable &t, int unroll, bool nt,
                                unsigned blocks, hipStream_t cs,
                                const PullDone *done)
 {
-    static const PullKernel variants[3] = {
-        {{k_pull_multi_done<1, true>, k_pull_multi_done<1, false>},
-         {k_pull_multi<1, true>, k_pull_multi<1, false>}},
-        {{k_pull_multi_done<8, true>, k_pull_multi_done<8, false>},
-         {k_pull_multi<8, true>, k_pull_multi<8, false>}},
-        {{k_pull_multi_done<4, true>, k_pull_multi_done<4, false>},
-         {k_pull_multi<4, true>, k_pull_multi<4, false>}}};
+    static const PullKernel variants[3] = {PULL_KERNELS(1), PULL_KERNELS(8),
+                                           PULL_KERNELS(4)};
     const PullKernel &k = variants[unroll == 1 ? 0 : unroll == 8 ? 1 : 2];
     if (done != nullptr)
-        hipLaunchKernelGGL(k.by_word[nt ? 0 : 1], dim3(blocks),
-                           dim3(PULL_THREADS), 0, cs, t, *done);
+        hipLaunchKernelGGL(k.by_word, dim3(blocks), dim3(PULL_THREADS), 0, cs,
+                           t, *done);
     else
         hipLaunchKernelGGL(k.by_event[nt ? 0 : 1], dim3(blocks),
                            dim3(PULL_THREADS), 0, cs, t);
@@ -280,10 +351,8 @@ static inline void launch_strided(const StridedTable &t, bool wide, bool parts,
                                   const PullDone *done)
 {
     static const StridedKernel variants[2][2] = {
-        {{k_pull_strided_done<true, true>, k_pull_strided<true, true>},
-         {k_pull_strided_done<true, false>, k_pull_strided<true, false>}},
-        {{k_pull_strided_done<false, true>, k_pull_strided<false, true>},
-         {k_pull_strided_done<false, false>, k_pull_strided<false, false>}}};
+        {STRIDED_KERNELS(true, true), STRIDED_KERNELS(true, false)},
+        {STRIDED_KERNELS(false, true), STRIDED_KERNELS(false, false)}};
     const StridedKernel &k = variants[wide ? 0 : 1][parts ? 0 : 1];
     if (done != nullptr)
         hipLaunchKernelGGL(k.by_word, dim3(blocks), dim3(PULL_THREADS), 0, cs,
@@ -291,6 +360,14 @@ static inline void launch_strided(const StridedTable &t, bool wide, bool parts,
     else
         hipLaunchKernelGGL(k.by_event, dim3(blocks), dim3(PULL_THREADS), 0, cs,
                            t);
+}
+
+#undef PULL_KERNELS
+#undef STRIDED_KERNELS
+
+static inline void launch_tail(uint64_t *word, uint64_t seq, hipStream_t cs)
+{
+    hipLaunchKernelGGL(k_pull_tail, dim3(1), dim3(1), 0, cs, word, seq);
 }
 
 } /* namespace mpix */
