@@ -35,6 +35,13 @@ step pingpong 120 mpiexec -np 2 bench/bin/pingpong 24 100
 step halo3d 90 mpiexec -np 2 bench/bin/halo3d 192 256 256 10
 step gemm_check 90 bench/bin/gemm_pready --check
 step gemm_overlap 120 mpiexec -np 2 bench/bin/gemm_pready 4096 4096 4096 5
+# every pull-kernel variant, launched directly, against the byte-exact
+# reference; a group that fails ends the row
+for g in contig-u1 contig-u4 contig-u8 strided-narrow strided-wide; do
+    f=$FAIL
+    step "pull_kernels_$g" 60 tools/bin/pull_kernels_check "$g"
+    [ "$FAIL" = "$f" ] || break
+done
 
 if [ "$MODE" = full ]; then
     # classic-protocol A/B (fast-wait is the default since r02)

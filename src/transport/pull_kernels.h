@@ -1,6 +1,8 @@
 /* mpix — the pull kernels of the native transport and their launch dispatch.
- * HIP only; included by native.cpp alone.  The host plans a batch
- * (pull_plan.h, strided_plan.h); what runs on the device is in here. */
+ * HIP only; included by native.cpp, and by
+ * tests/native/pull_kernels_check.hip, which launches every variant in here
+ * directly.  The host plans a batch (pull_plan.h, strided_plan.h); what runs
+ * on the device is in here. */
 #ifndef MPIX_TRANSPORT_PULL_KERNELS_H
 #define MPIX_TRANSPORT_PULL_KERNELS_H
 

@@ -6,8 +6,14 @@ Payloads are position-dependent (byte i of the whole source tensor is
 destination sits inside a larger tensor filled with a sentinel, and the
 sentinel bytes before, between and after the destinations must survive.
 
-Tile sizes are 16384 B (U = 4) and 32768 B (U = 8): the lengths below are one
-vector, one tile -/+ 16 B for both, and tails (n % 16 != 0).
+This file runs the default kernel only: unroll 4 (tiles of 16384 B),
+write-through with the completion word.  The lengths below are one vector,
+one tile -/+ 16 B and tails (n % 16 != 0); they bracket 32768 B as well, the
+tile of unroll 8, but here that is just two tiles of unroll 4.  Unroll 1 and
+8 and the nontemporal and plain kernels run in
+tests/test_pull_kernels_gpu.py (every variant, launched directly, against a
+byte-exact reference) and tests/test_pull_variants_gpu.py (selected by
+MPIX_PULL_UNROLL / MPIX_PULL_NT through the runtime).
 """
 import pytest
 
