@@ -42,8 +42,10 @@ $(PYEXT): mpix/_core.o $(OBJS)
 src/transport/native.o: src/transport/pull_plan.h src/transport/layout.h \
                         src/transport/strided_plan.h src/transport/part_run.h \
                         src/transport/done_ring.h src/transport/pull_kernels.h \
-                        src/transport/shm_ring.h
+                        src/transport/shm_ring.h src/transport/reduce.h \
+                        src/transport/reduce_plan.h
 src/enqueue.o src/partitioned.o: src/transport/layout.h
+src/enqueue.o: src/transport/reduce.h
 
 $(LIB): $(OBJS)
 	$(HIPCC) --offload-arch=$(GPU_ARCH) $(OBJS) $(LDFLAGS) -o $@
@@ -65,4 +67,15 @@ mpi4check:
 	$(HIPCC) $(CXXFLAGS) -DMPIX_MPI_PARTITIONED -c src/enqueue.cpp -o $(MPI4CHECK_DIR)/enq.o
 	@echo "mpi4check: MPI-4 partitioned passthrough compiles both ways"
 
-.PHONY: all clean python mpi4check
+# The check programs of the reducing receive: reduce.h and reduce_plan.h
+# against independent references on the CPU (ASan + UBSan), and the reduce
+# kernels launched directly on a GPU (tests/test_reduce_ref.py,
+# tests/test_reduce_kernels_gpu.py).
+reduce_check:
+	$(MAKE) -C tools bin/reduce_check
+	tools/bin/reduce_check
+
+reduce_kernels_check:
+	$(MAKE) -C tools bin/reduce_kernels_check
+
+.PHONY: all clean python mpi4check reduce_check reduce_kernels_check

@@ -98,6 +98,59 @@ int MPIX_Irecv_strided_enqueue(void *buf, const MPIX_Layout *layout,
                                int source, int tag, MPI_Comm comm,
                                MPIX_Request *request, int qtype, void *queue);
 
+/* Reducing receives: the message is COMBINED into the buffer instead of
+ * overwriting it.  On completion buf[i] = buf[i] op msg[i] for every whole
+ * element of the message; exactly one combine happens per element per
+ * receive, so the result is bit-defined.  Nothing changes for the sender: a
+ * message is still its bytes, and MPIX_Isend_enqueue or MPIX_Psend_init
+ * match.  Device buffers are combined inside the receiver's pull kernel (no
+ * staging buffer, no add kernel behind the wait), host buffers as the chunks
+ * arrive.  mpix has its own element types because MPI 3.1 has no bf16 or
+ * f16 datatype.
+ *
+ * Numeric definition, for host and device buffers alike:
+ *   MPIX_F32, MPIX_F64  IEEE add
+ *   MPIX_F16            the correctly rounded half sum, rounded once
+ *   MPIX_BF16           round-to-nearest-even to bf16 of the f32 sum of the
+ *                       two widened values (what torch computes on the CPU)
+ *   MPIX_I32, MPIX_I64  two's-complement wrap
+ *   MPIX_MAX, MPIX_MIN  the larger / smaller value
+ * NaNs and the sign of a zero result under MAX/MIN are unspecified; subnormal
+ * f32 and bf16 results follow the compiler's default denormal mode.
+ *
+ * Requests behave like those of the plain receives: stream and graph queues,
+ * captures, fast-wait, MPIX_Wait*_enqueue, MPIX_Wait[all], MPIX_Request_free,
+ * the status byte count, unexpected messages; a zero-byte message leaves the
+ * buffer untouched.  For partitions: MPIX_Start, MPIX_Parrived on host and
+ * device, MPIX_Prequest_create and reuse across iterations are the same
+ * calls.  Reuse ACCUMULATES AGAIN on every iteration: a replayed capture or
+ * a restarted partitioned request adds to what the buffer holds, so the user
+ * resets the buffer between iterations, with work that finished before the
+ * receive is triggered (before MPIX_Start for partitions).
+ *
+ * Several pending reducing receives into the same or overlapping device
+ * memory are allowed, provided all of them are reducing (one receive per
+ * peer accumulating into one buffer): the library serialises them, and the
+ * result depends on arrival order only through float rounding.
+ *
+ * Errors at the call: MPI_ERR_ARG for an unknown type or op, a buf that is
+ * not aligned to the element size, a negative count; MPI_ERR_TYPE for a
+ * communicator served by the MPI passthrough and under
+ * MPIX_MPI_PARTITIONED=1.  As the completion status, with the sender still
+ * acked and completing: MPI_ERR_TRUNCATE for a message longer than the
+ * buffer (the elements that fit are combined); MPI_ERR_TYPE, the buffer
+ * untouched, when the message length is not a multiple of the element size,
+ * a device sender's source address is not element-aligned, the sender's
+ * message is strided, or one side is in host memory and the other in device
+ * memory (a device receive that gets host chunks included).
+ * Not supported: reducing strided receives, user-defined ops. */
+enum { MPIX_F32, MPIX_F64, MPIX_BF16, MPIX_F16, MPIX_I32, MPIX_I64 };
+enum { MPIX_SUM, MPIX_MAX, MPIX_MIN };
+
+int MPIX_Irecv_reduce_enqueue(void *buf, int count, int type, int op,
+                              int source, int tag, MPI_Comm comm,
+                              MPIX_Request *request, int qtype, void *queue);
+
 int MPIX_Wait_enqueue(MPIX_Request *req, MPI_Status *status, int qtype,
                       void *queue);
 int MPIX_Waitall_enqueue(int count, MPIX_Request *reqs, MPI_Status *statuses,
@@ -148,6 +201,15 @@ int MPIX_Precv_init_strided(void *buf, int partitions,
                             int64_t part_stride, int source, int tag,
                             MPI_Comm comm, MPI_Info info,
                             MPIX_Request *request);
+
+/* Reducing variant of MPIX_Precv_init: `count` elements of `type` per
+ * partition, each arriving partition combined into its slice with `op`
+ * (semantics, numeric definition and errors: MPIX_Irecv_reduce_enqueue
+ * above).  The sender uses MPIX_Psend_init with the same bytes per partition.
+ * Device partitions made ready together are combined by one kernel entry. */
+int MPIX_Precv_init_reduce(void *buf, int partitions, MPI_Count count,
+                           int type, int op, int source, int tag,
+                           MPI_Comm comm, MPI_Info info, MPIX_Request *request);
 
 /* Build a device-resident handle for __device__ MPIX_Pready/Parrived. */
 int MPIX_Prequest_create(MPIX_Request request, MPIX_Prequest *prequest);

@@ -192,6 +192,70 @@ def irecv_graph(buf, source, tag=0, nbytes=None):
     return _sendrecv(False, buf, source, tag, QUEUE_GRAPH, None, nbytes)
 
 
+# ------------------------- reducing receives ------------------------------
+
+_REDUCE_OPS = {"sum": _C.SUM, "max": _C.MAX, "min": _C.MIN}
+_REDUCE_TYPES = {"float32": _C.F32, "float64": _C.F64, "bfloat16": _C.BF16,
+                 "float16": _C.F16, "int32": _C.I32, "int64": _C.I64}
+
+
+def _reduce_args(buf, op):
+    """(address, elements, type, op) of a reducing receive into `buf`: a
+    contiguous torch tensor (float32, float64, bfloat16, float16, int32,
+    int64) or numpy array (the same without bfloat16).  ValueError for any
+    other dtype, a non-contiguous view or an unknown op."""
+    if op not in _REDUCE_OPS:
+        raise ValueError(f"unknown reduce op {op!r}: one of "
+                         f"{sorted(_REDUCE_OPS)}")
+    if hasattr(buf, "data_ptr"):  # torch tensor
+        name = str(buf.dtype).replace("torch.", "")
+        contiguous = buf.is_contiguous()
+        addr, count = buf.data_ptr(), buf.numel()
+    elif hasattr(buf, "ctypes"):  # numpy array
+        name = buf.dtype.name
+        contiguous = bool(buf.flags["C_CONTIGUOUS"])
+        addr, count = buf.ctypes.data, buf.size
+    else:
+        raise TypeError(f"unsupported buffer type {type(buf)}: a reducing "
+                        f"receive takes its element type from the dtype")
+    if name not in _REDUCE_TYPES:
+        raise ValueError(f"cannot reduce into dtype {name}: one of "
+                         f"{sorted(_REDUCE_TYPES)}")
+    if not contiguous:
+        raise ValueError("a reducing receive needs a contiguous buffer "
+                         "(reducing strided receives are not supported)")
+    return int(addr), int(count), _REDUCE_TYPES[name], _REDUCE_OPS[op]
+
+
+def irecv_reduce_enqueue(buf, source, op="sum", tag=0, stream=None):
+    """Receive a message and COMBINE it into `buf`: on completion
+    buf[i] = buf[i] op msg[i] (op: "sum", "max", "min").  The element type
+    is the dtype of `buf`; the sender uses the plain calls.  The request
+    behaves like irecv_enqueue's."""
+    addr, count, typ, rop = _reduce_args(buf, op)
+    return _C.irecv_reduce(addr, count, typ, rop, source, tag, QUEUE_STREAM,
+                           _stream_addr(stream))
+
+
+def irecv_reduce_graph(buf, source, op="sum", tag=0):
+    """Graph-construction variant: returns (request, graph_handle).  Every
+    launch of the graph combines again."""
+    addr, count, typ, rop = _reduce_args(buf, op)
+    return _C.irecv_reduce(addr, count, typ, rop, source, tag, QUEUE_GRAPH, 0)
+
+
+def precv_reduce_init(buf, partitions, source, op="sum", tag=0):
+    """Partitioned reducing receive: `buf` is cut into `partitions` equal
+    slices and each arriving partition is combined into its slice.  Every
+    iteration (start) accumulates again; reset `buf` in between."""
+    addr, count, typ, rop = _reduce_args(buf, op)
+    if partitions <= 0 or count % partitions != 0:
+        raise ValueError(f"{count} elements do not divide evenly into "
+                         f"{partitions} partitions")
+    return _C.precv_init_reduce(addr, partitions, count // partitions, typ,
+                                rop, source, tag)
+
+
 def waitall_graph(reqs):
     return _C.waitall_graph(list(reqs))
 

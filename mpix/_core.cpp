@@ -117,6 +117,18 @@ PYBIND11_MODULE(_C, m)
     m.attr("QUEUE_GRAPH") = (int)MPIX_QUEUE_HIP_GRAPH;
     m.attr("ANY_SOURCE") = (int)MPI_ANY_SOURCE;
     m.attr("ANY_TAG") = (int)MPI_ANY_TAG;
+    m.attr("ERR_ARG") = (int)MPI_ERR_ARG;
+    m.attr("ERR_TYPE") = (int)MPI_ERR_TYPE;
+    m.attr("ERR_TRUNCATE") = (int)MPI_ERR_TRUNCATE;
+    m.attr("F32") = (int)MPIX_F32;
+    m.attr("F64") = (int)MPIX_F64;
+    m.attr("BF16") = (int)MPIX_BF16;
+    m.attr("F16") = (int)MPIX_F16;
+    m.attr("I32") = (int)MPIX_I32;
+    m.attr("I64") = (int)MPIX_I64;
+    m.attr("SUM") = (int)MPIX_SUM;
+    m.attr("MAX") = (int)MPIX_MAX;
+    m.attr("MIN") = (int)MPIX_MIN;
 
     py::class_<MxRequest>(m, "Request")
         .def("is_null", [](const MxRequest &r) {
@@ -208,6 +220,35 @@ PYBIND11_MODULE(_C, m)
                   throw std::runtime_error(
                       "MPIX_I" + std::string(is_send ? "send" : "recv") +
                       "_strided_enqueue failed, rc=" + std::to_string(rc));
+              }
+              py::object pr =
+                  py::cast(r, py::return_value_policy::take_ownership);
+              if (qtype == MPIX_QUEUE_HIP_GRAPH)
+                  return py::make_tuple(pr, (uintptr_t)g);
+              return pr;
+          });
+
+    /* reducing receive of `count` elements of `type` (MPIX_F32 ..) combined
+     * with `op` (MPIX_SUM ..); qtype GRAPH returns (request, graph), STREAM
+     * the request.  The rc is in the message: Python tests tell MPI_ERR_ARG
+     * from MPI_ERR_TYPE by it. */
+    m.def("irecv_reduce",
+          [](uintptr_t buf, int64_t count, int type, int op, int source,
+             int tag, int qtype, uintptr_t stream) -> py::object {
+              auto *r = new MxRequest();
+              hipGraph_t g = nullptr;
+              void *q = qtype == MPIX_QUEUE_HIP_GRAPH ? (void *)&g
+                                                      : (void *)&stream;
+              int rc = count > INT32_MAX
+                  ? MPI_ERR_ARG
+                  : MPIX_Irecv_reduce_enqueue((void *)buf, (int)count, type,
+                                              op, source, tag, MPI_COMM_WORLD,
+                                              &r->req, qtype, q);
+              if (rc != 0) {
+                  delete r;
+                  throw std::runtime_error(
+                      "MPIX_Irecv_reduce_enqueue failed, rc=" +
+                      std::to_string(rc));
               }
               py::object pr =
                   py::cast(r, py::return_value_policy::take_ownership);
@@ -312,6 +353,24 @@ PYBIND11_MODULE(_C, m)
                   throw std::runtime_error(
                       "MPIX_P" + std::string(is_send ? "send" : "recv") +
                       "_init_strided failed, rc=" + std::to_string(rc));
+              }
+              return r;
+          },
+          py::return_value_policy::take_ownership);
+
+    m.def("precv_init_reduce",
+          [](uintptr_t buf, int partitions, int64_t count_per_part, int type,
+             int op, int source, int tag) {
+              auto *r = new MxRequest();
+              int rc = MPIX_Precv_init_reduce((void *)buf, partitions,
+                                              (MPI_Count)count_per_part, type,
+                                              op, source, tag, MPI_COMM_WORLD,
+                                              MPI_INFO_NULL, &r->req);
+              if (rc != 0) {
+                  delete r;
+                  throw std::runtime_error(
+                      "MPIX_Precv_init_reduce failed, rc=" +
+                      std::to_string(rc));
               }
               return r;
           },

@@ -19,6 +19,7 @@
 
 #include "internal.h"
 #include "transport/layout.h"
+#include "transport/reduce.h"
 
 namespace mpix {
 
@@ -277,12 +278,37 @@ static int fire_trigger(int idx, int qtype, void *queue, Request *req)
     return MPI_SUCCESS;
 }
 
-/* Common body of Isend/Irecv_enqueue and their strided variants (`layout`
- * non-null: count and datatype are ignored, the message is the layout's). */
+static_assert(MPIX_F32 == RED_F32 && MPIX_F64 == RED_F64 &&
+              MPIX_BF16 == RED_BF16 && MPIX_F16 == RED_F16 &&
+              MPIX_I32 == RED_I32 && MPIX_I64 == RED_I64 &&
+              MPIX_SUM == RED_SUM && MPIX_MAX == RED_MAX &&
+              MPIX_MIN == RED_MIN, "mpix.h and transport/reduce.h disagree");
+
+int reduce_check_args(const RedSpec &red, const void *buf, int *esize)
+{
+    if (!reduce_type_ok(red.type) || !reduce_op_ok(red.op)) {
+        MPIX_ERR("reducing receive: unknown element type %d or op %d",
+                 red.type, red.op);
+        return MPI_ERR_ARG;
+    }
+    *esize = (int)reduce_elem_size(red.type);
+    if (((uintptr_t)buf % (uintptr_t)*esize) != 0) {
+        MPIX_ERR("reducing receive: buffer %p is not aligned to its %d-byte "
+                 "elements", buf, *esize);
+        return MPI_ERR_ARG;
+    }
+    return MPI_SUCCESS;
+}
+
+/* Common body of Isend/Irecv_enqueue and their variants.  `layout` non-null
+ * (strided): count and datatype are ignored, the message is the layout's.
+ * `red` non-null (reducing receive): datatype is ignored, count is in
+ * elements of red->type. */
 static int enqueue_sendrecv(bool is_send, void *buf, int count,
                             MPI_Datatype datatype, int peer, int tag,
                             MPI_Comm comm, MPIX_Request *request, int qtype,
-                            void *queue, const MPIX_Layout *layout = nullptr)
+                            void *queue, const MPIX_Layout *layout = nullptr,
+                            const RedSpec *red = nullptr)
 {
     State *s = g_state;
     if (s == nullptr) {
@@ -310,6 +336,10 @@ static int enqueue_sendrecv(bool is_send, void *buf, int count,
         datatype = MPI_BYTE;
         uint64_t nb = layout_bytes(norm);
         count = nb > (uint64_t)INT32_MAX ? INT32_MAX : (int)nb;
+    } else if (red != nullptr) {
+        int rc = reduce_check_args(*red, buf, &tsz);
+        if (rc != MPI_SUCCESS) return rc;
+        datatype = MPI_BYTE;
     } else {
         MPIX_CHECK(datatype_size(datatype, &tsz));
     }
@@ -317,6 +347,11 @@ static int enqueue_sendrecv(bool is_send, void *buf, int count,
     uint32_t comm_id = 0;
     bool native_ok = false;
     MPIX_CHECK(resolve_peer(comm, peer, &peer_world, &comm_id, &native_ok));
+    if (red != nullptr && !native_ok) {
+        MPIX_ERR("reducing receives are served by the native transport only; "
+                 "this communicator resolves to the MPI passthrough");
+        return MPI_ERR_TYPE;
+    }
     if (layout != nullptr && !native_ok) {
         MPIX_ERR("strided transfers are served by the native transport only; "
                  "this communicator resolves to the MPI passthrough");
@@ -337,6 +372,13 @@ static int enqueue_sendrecv(bool is_send, void *buf, int count,
         op->bytes = layout_bytes(norm);
         op->strided = !layout_is_contiguous(norm);
         op->layout = norm;
+    }
+    if (red != nullptr) {
+        op->reduce = true;
+        op->red_type = (uint8_t)red->type;
+        op->red_op = (uint8_t)red->op;
+        op->count = op->bytes > (uint64_t)INT32_MAX ? INT32_MAX
+                                                    : (int)op->bytes;
     }
     op->peer = peer;
     op->peer_world = peer_world;
@@ -395,6 +437,16 @@ extern "C" int MPIX_Irecv_enqueue(void *buf, int count, MPI_Datatype datatype,
 {
     return enqueue_sendrecv(false, buf, count, datatype, source, tag, comm,
                             request, qtype, queue);
+}
+
+extern "C" int MPIX_Irecv_reduce_enqueue(void *buf, int count, int type,
+                                         int op, int source, int tag,
+                                         MPI_Comm comm, MPIX_Request *request,
+                                         int qtype, void *queue)
+{
+    const RedSpec red{type, op};
+    return enqueue_sendrecv(false, buf, count, MPI_BYTE, source, tag, comm,
+                            request, qtype, queue, nullptr, &red);
 }
 
 extern "C" int MPIX_Isend_strided_enqueue(const void *buf,

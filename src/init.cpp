@@ -643,6 +643,15 @@ extern "C" int MPIX_Finalize(void)
                     "with a partition level\n", s->world_rank,
                     (unsigned long)s->run_copy, (unsigned long)s->run_folded,
                     (unsigned long)s->run_parts);
+        if (s->reduce_launches)
+            fprintf(stderr,
+                    "[mpix stats r%d] reducing receives: %lu launches for "
+                    "%lu receives in %lu entries, %lu runs taken as one "
+                    "entry\n", s->world_rank,
+                    (unsigned long)s->reduce_launches,
+                    (unsigned long)s->reduce_msgs,
+                    (unsigned long)s->reduce_entries,
+                    (unsigned long)s->run_reduce);
         if (s->bleg_first_seen) {
             /* on its own line and in none of the means below: this launch
              * loads the code object */

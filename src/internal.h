@@ -145,6 +145,11 @@ struct Op {
      * contiguous) and `bytes` is the message length */
     bool strided = false;
     MPIX_Layout layout = {};
+    /* reducing receive (MPIX_Irecv_reduce_enqueue, MPIX_Precv_init_reduce):
+     * the message is combined into buf, element type and op as in
+     * transport/reduce.h; bytes is a multiple of the element size */
+    bool reduce = false;
+    uint8_t red_type = 0, red_op = 0;
     uint32_t pseq = 0;              /* partitioned iteration number */
     Request *req = nullptr;         /* owning request */
 
@@ -185,6 +190,7 @@ struct Op {
         comm = MPI_COMM_NULL; comm_id = 0; buf_is_device = false;
         native_route = true;
         strided = false; layout = MPIX_Layout{};
+        reduce = false; red_type = red_op = 0;
         partition = -1; pseq = 0; req = nullptr;
         t_enq_ns = 0; t_issue_ns = 0;
         ch_done.store(0, std::memory_order_relaxed);
@@ -389,6 +395,10 @@ struct State {
     /* runs taken on the fast path, by the pull they became: one contiguous
      * copy, one folded strided entry, one entry with a partition level */
     uint64_t run_copy = 0, run_folded = 0, run_parts = 0;
+    /* reducing receives: launches of the reduce kernel, the receives and
+     * the table entries they carried, runs taken as one reduce entry */
+    uint64_t reduce_launches = 0, reduce_msgs = 0, reduce_entries = 0;
+    uint64_t run_reduce = 0;
     /* event -> last SEND op of a loopback batch COMPLETED (the sends are
      * completed by the same walk, behind the receives) */
     uint64_t bleg_send_done_ns = 0, bleg_send_done_n = 0;
@@ -465,6 +475,15 @@ int datatype_size(MPI_Datatype dt, int *size_out);
  * comm_id 0 = WORLD, 1 = SELF; other comms are MPI-mode passthrough only. */
 int resolve_peer(MPI_Comm comm, int rank, int *world_rank_out,
                  uint32_t *comm_id_out, bool *native_ok_out);
+
+/* What a reducing receive adds to a plain one (enqueue.cpp, partitioned.cpp):
+ * MPIX_F32.. and MPIX_SUM.. of mpix.h. */
+struct RedSpec {
+    int type, op;
+};
+/* MPI_SUCCESS and *esize, or MPI_ERR_ARG: unknown type or op, or `buf` not
+ * aligned to the element size */
+int reduce_check_args(const RedSpec &red, const void *buf, int *esize);
 
 /* Write an MPI_Status (MPICH layout) from a transport completion. */
 void fill_status(MPI_Status *st, const ChStatus &cs);

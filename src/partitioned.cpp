@@ -24,14 +24,17 @@
 
 namespace mpix {
 
-/* Common body of the plain and the strided init calls.  `layout` non-null
- * (the strided calls): count and datatype are ignored, partition p is the
- * buffer at buf + p * part_stride laid out as *layout. */
+/* Common body of the plain, the strided and the reducing init calls.
+ * `layout` non-null (the strided calls): count and datatype are ignored,
+ * partition p is the buffer at buf + p * part_stride laid out as *layout.
+ * `red` non-null (MPIX_Precv_init_reduce): datatype is ignored, count is in
+ * elements of red->type. */
 static int psend_precv_init(bool is_send, void *buf, int partitions,
                             MPI_Count count, MPI_Datatype datatype, int peer,
                             int tag, MPI_Comm comm, MPIX_Request *request,
                             const MPIX_Layout *layout = nullptr,
-                            int64_t part_stride = 0)
+                            int64_t part_stride = 0,
+                            const RedSpec *red = nullptr)
 {
     State *s = g_state;
     if (s == nullptr) return MPI_ERR_OTHER;
@@ -69,6 +72,14 @@ static int psend_precv_init(bool is_send, void *buf, int partitions,
         datatype = MPI_BYTE;
         tsz = 1;
         count = (MPI_Count)layout_bytes(norm);
+    } else if (red != nullptr) {
+        /* `count` elements of red->type per partition, kept as bytes */
+        int esize = 0;
+        int rc = reduce_check_args(*red, buf, &esize);
+        if (rc != MPI_SUCCESS) return rc;
+        datatype = MPI_BYTE;
+        tsz = 1;
+        count *= (MPI_Count)esize;
     } else {
         MPIX_CHECK(datatype_size(datatype, &tsz));
     }
@@ -97,6 +108,12 @@ static int psend_precv_init(bool is_send, void *buf, int partitions,
     if (layout != nullptr && (!native_ok || mpi_native)) {
         MPIX_ERR("strided partitions are served by the native transport only; "
                  "this communicator or the MPI-4.0 passthrough "
+                 "(MPIX_MPI_PARTITIONED=1) is routed through MPI");
+        return MPI_ERR_TYPE;
+    }
+    if (red != nullptr && (!native_ok || mpi_native)) {
+        MPIX_ERR("reducing partitions are served by the native transport "
+                 "only; this communicator or the MPI-4.0 passthrough "
                  "(MPIX_MPI_PARTITIONED=1) is routed through MPI");
         return MPI_ERR_TYPE;
     }
@@ -168,6 +185,11 @@ static int psend_precv_init(bool is_send, void *buf, int partitions,
             op->strided = !layout_is_contiguous(norm);
             op->layout = norm;
         }
+        if (red != nullptr) {
+            op->reduce = true;
+            op->red_type = (uint8_t)red->type;
+            op->red_op = (uint8_t)red->op;
+        }
         /* native shm/xGMI for WORLD/SELF; MPI transport for arbitrary comms
          * (header-routed partition messages) and the MPI-4.0 passthrough */
         op->native_route = native_ok && !req->mpi_part_native;
@@ -200,6 +222,17 @@ extern "C" int MPIX_Precv_init(void *buf, int partitions, MPI_Count count,
     (void)info;
     return psend_precv_init(false, buf, partitions, count, datatype, source,
                             tag, comm, request);
+}
+
+extern "C" int MPIX_Precv_init_reduce(void *buf, int partitions,
+                                      MPI_Count count, int type, int op,
+                                      int source, int tag, MPI_Comm comm,
+                                      MPI_Info info, MPIX_Request *request)
+{
+    (void)info;
+    const RedSpec red{type, op};
+    return psend_precv_init(false, buf, partitions, count, MPI_BYTE, source,
+                            tag, comm, request, nullptr, 0, &red);
 }
 
 extern "C" int MPIX_Psend_init_strided(const void *buf, int partitions,

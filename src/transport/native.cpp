@@ -17,6 +17,10 @@
  *                 Consecutive partitions of one request go out as a RUN:
  *                 one descriptor, one pull, one DONE per acked range
  *                 (part_run.h); an ack to ourselves skips the ring.
+ *                 A REDUCING receive (Op::reduce) combines the message into
+ *                 its buffer inside the pull: k_pull_reduce, planned by
+ *                 reduce_plan.h, the combine defined by reduce.h; host
+ *                 buffers combine chunk by chunk (reduce_host).
  *  host data      sender stages through the shm chunk ring (64 KiB chunks,
  *                 credit-based flow control); the receiver copies chunks
  *                 straight into the posted buffer (or an unexpected-message
@@ -53,6 +57,8 @@
 #include "part_run.h"
 #include "pull_kernels.h"
 #include "pull_plan.h"
+#include "reduce.h"
+#include "reduce_plan.h"
 #include "shm_ring.h"
 #include "strided_plan.h"
 
@@ -243,7 +249,9 @@ private:
         Op *op = nullptr;       /* matched recv, or null */
         std::vector<char> heap; /* unexpected host payload buffer */
         uint64_t got = 0;       /* host bytes received so far */
-        bool kind_mismatch = false; /* strided msg between host and device */
+        bool kind_mismatch = false; /* payload dropped, MPI_ERR_TYPE: strided
+                                       msg between host and device, or one
+                                       a reducing receive cannot combine */
     };
     std::list<InboundMsg> inbound_;                 /* arrival order */
     std::unordered_map<uint64_t, InboundMsg *> inbound_by_token_;
@@ -333,6 +341,19 @@ private:
     std::vector<PendingStrided> pend_strided_;
     StridedTable splan_{}; /* scratch of flush_strided; passed by value */
     bool strided_div64_ = false; /* MPIX_STRIDED_DIV64=1: see plan_strided */
+
+    /* reducing pulls (Op::reduce) collected this progress pass: k_pull_reduce
+     * launches of up to MPIX_PULL_BATCH of them, cut where destinations
+     * overlap (reduce_plan.h), completed through batches_ like the others.
+     * They all go to the copy stream itself, so launches with overlapping
+     * destinations run one after the other. */
+    struct PendingReduce {
+        PendingPull pp;
+        uint32_t type, op;
+    };
+    std::vector<PendingReduce> pend_reduce_;
+    ReduceTable rplan_{}; /* scratch of flush_reduce; passed by value */
+    hipStream_t reduce_cs_ = nullptr; /* stream of the last reduce launch */
 
     /* ---- shm ---- */
     ShmGeom geom_{};
@@ -441,7 +462,9 @@ private:
     void progress_copies();
     void flush_pulls();
     void flush_strided();
+    void flush_reduce();
     void fail_kind_mismatch(InboundMsg &m);
+    const char *reduce_reject(const InboundMsg &m, const void *src) const;
     void handle_desc(int src, const Desc &d, const char *stage_base);
     bool try_run_fast_path(int src, const Desc &d, uint32_t k);
     Desc desc_for(const Op *op, DescType type) const;
@@ -583,6 +606,7 @@ void NativeTransport::shutdown()
     done_words_d_ = nullptr;
     done_counters_ = nullptr;
     done_mode_ = PullDoneMode::EVENT;
+    reduce_cs_ = nullptr;
     for (hipStream_t *s : {&copy_stream_, &copy_big_, &copy_retired_}) {
         if (*s) (void)hipStreamDestroy(*s);
         *s = nullptr;
@@ -640,6 +664,7 @@ void NativeTransport::progress()
     for (int s = 0; s < size_; s++) drain_inbox(s);
     flush_pulls();
     flush_strided();
+    flush_reduce();
     progress_copies();
 
     /* retry queued DONE acks */
@@ -962,8 +987,15 @@ bool NativeTransport::try_run_fast_path(int src, const Desc &d, uint32_t k)
     const bool plain = !s_strided && !op->strided &&
                        d.part_stride == (int64_t)d.msg_bytes &&
                        rq->part_stride == (int64_t)d.msg_bytes;
+    /* Reducing partitions (one request: all of the range or none) are taken
+     * in the plain shape only, as ONE reduce entry of k * msg_bytes.  A
+     * strided or gapped sender expands, and start_dev_copy gives every
+     * partition its status. */
+    if (op->reduce &&
+        (!plain || d.msg_bytes % reduce_elem_size(op->red_type) != 0))
+        return false;
     /* today's run, and today's rule for it: a misaligned one expands into
-     * k hipMemcpyAsync */
+     * k hipMemcpyAsync (reducing: k entries on the element path) */
     if (plain && ((((uintptr_t)op->buf) | ((uintptr_t)sp)) & 15) != 0)
         return false;
     posted_recvs_.erase(posted_recvs_.begin() + first,
@@ -974,6 +1006,11 @@ bool NativeTransport::try_run_fast_path(int src, const Desc &d, uint32_t k)
                          (uint64_t)k * d.msg_bytes, seen_ns(op, d),
                          d.partition, k};
     g_state->run_fast_msgs += k;
+    if (op->reduce) {
+        pend_reduce_.push_back(PendingReduce{pp, op->red_type, op->red_op});
+        g_state->run_reduce++;
+        return true;
+    }
     if (plain) {
         pend_pulls_.push_back(pp);
         g_state->run_copy++;
@@ -1045,14 +1082,25 @@ void NativeTransport::attach(InboundMsg &m, Op *op)
         start_dev_copy(m);
         return;
     }
-    if ((op->strided || (m.d.flags & DESCF_STRIDED)) && op->buf_is_device) {
+    const char *why = op->reduce ? reduce_reject(m, nullptr) : nullptr;
+    if (why != nullptr) {
+        MPIX_ERR("reducing receive from rank %d, tag %d fails with "
+                 "MPI_ERR_TYPE: %s", m.src, m.d.tag, why);
+        m.kind_mismatch = true;
+    } else if ((op->strided || (m.d.flags & DESCF_STRIDED)) &&
+               op->buf_is_device) {
         fail_kind_mismatch(m);
     } else if (m.got > 0 && !m.heap.empty()) {
         /* host message: move already-buffered bytes (message order) into
          * the user buffer */
         uint64_t n = m.got;
         if (n > op->bytes) n = op->bytes;
-        if (n > 0 && op->strided)
+        if (n > 0 && op->reduce)
+            /* whole elements: see deliver_chunk */
+            reduce_host(op->buf, m.heap.data(),
+                        n / reduce_elem_size(op->red_type), op->red_type,
+                        op->red_op);
+        else if (n > 0 && op->strided)
             layout_copy_in(op->buf, op->layout, 0, m.heap.data(), n);
         else if (n > 0)
             memcpy_auto(op->buf, m.heap.data(), n);
@@ -1073,7 +1121,19 @@ void NativeTransport::deliver_chunk(InboundMsg &m, const Desc &d,
          * MPI_ERR_TYPE */
         if (m.kind_mismatch)
             n = 0;
-        if (n > 0 && m.op->strided)
+        /* A reducing receive combines the chunk where a plain one copies
+         * it.  No element straddles two chunks: a chunk starts at a
+         * multiple of CHUNK_BYTES, which every element size divides, so it
+         * holds whole elements except possibly at the message's end, and a
+         * message that ends inside an element was rejected in attach.  The
+         * receive's own length is a multiple of the element size too, so a
+         * truncated chunk still ends on an element. */
+        static_assert(CHUNK_BYTES % 8 == 0, "chunks hold whole elements");
+        if (n > 0 && m.op->reduce)
+            reduce_host((char *)m.op->buf + d.chunk_off, src_chunk,
+                        n / reduce_elem_size(m.op->red_type), m.op->red_type,
+                        m.op->red_op);
+        else if (n > 0 && m.op->strided)
             layout_copy_in(m.op->buf, m.op->layout, d.chunk_off, src_chunk, n);
         else if (n > 0)
             memcpy_auto((char *)m.op->buf + d.chunk_off, src_chunk, n);
@@ -1111,6 +1171,25 @@ void NativeTransport::fail_kind_mismatch(InboundMsg &m)
                  "memory (device or host): message from rank %d, tag %d "
                  "fails with MPI_ERR_TYPE", m.src, m.d.tag);
     m.kind_mismatch = true;
+}
+
+/* Why the reducing receive matched to `m` cannot combine the message (it
+ * then completes with MPI_ERR_TYPE, its buffer untouched), or nullptr.
+ * `src`: the sender's mapped address, for a device message. */
+const char *NativeTransport::reduce_reject(const InboundMsg &m,
+                                           const void *src) const
+{
+    const Op *op = m.op;
+    const uint32_t esize = reduce_elem_size(op->red_type);
+    const bool dev_msg = m.d.type == DESC_DEV_NOTIFY;
+    if (m.d.flags & DESCF_STRIDED) return "the sender's message is strided";
+    if (m.d.msg_bytes % esize != 0)
+        return "the message length is not a multiple of the element size";
+    if (dev_msg != op->buf_is_device)
+        return "one side is in host memory and the other in device memory";
+    if (dev_msg && ((uintptr_t)src % esize) != 0)
+        return "the sender's address is not aligned to the element size";
+    return nullptr;
 }
 
 void *NativeTransport::map_remote(const Desc &d)
@@ -1167,9 +1246,29 @@ void NativeTransport::start_dev_copy(InboundMsg &m)
         fail_dev_recv(m, st);
         return;
     }
+    if (op->reduce) {
+        if (const char *why = reduce_reject(m, src)) {
+            MPIX_ERR("reducing receive from rank %d, tag %d fails with "
+                     "MPI_ERR_TYPE: %s", m.src, m.d.tag, why);
+            st.bytes = 0;
+            st.err = MPI_ERR_TYPE;
+            fail_dev_recv(m, st);
+            return;
+        }
+    }
     const uint64_t n = st.bytes;
     const PendingPull pp{op, m.src, m.d.token, st, op->buf, src, n,
                          seen_ns(op, m.d), m.d.partition, 1};
+    /* A reducing receive is always an entry of the reduce kernel, by the
+     * vector or the element path: never hipMemcpyAsync, never a strided
+     * entry.  n is a multiple of the element size (the message's length
+     * is, and a truncated one is cut to the receive's).  A zero-byte
+     * message falls through to the batch of one that copies nothing. */
+    if (op->reduce && n > 0) {
+        pend_reduce_.push_back(PendingReduce{pp, op->red_type, op->red_op});
+        erase_inbound(&m);
+        return;
+    }
     /* The shader pull path requires (a) a device destination — dereferencing
      * a pageable host pointer from a kernel faults on non-XNACK systems —
      * and (b) 16-byte alignment on both sides (user buffers can be
@@ -1404,6 +1503,63 @@ void NativeTransport::flush_strided()
             fprintf(stderr, "[mpix trace] strided pull batch n=%zu tiles=%lu "
                     "total=%lu B wide=%d parts=%d\n", n, (unsigned long)tiles,
                     (unsigned long)total, (int)wide, (int)parts);
+    }
+}
+
+/* The reducing pulls of this pass: one k_pull_reduce launch, and another
+ * for every entry whose destination overlaps one already planned and for
+ * every MPIX_PULL_BATCH entries.  All of them go to the copy stream itself,
+ * whatever their size: a later launch must run behind an earlier one that
+ * combined into the same bytes (pull_kernels.h on why it then sees them).
+ * Should the copy stream have been replaced since the last reduce launch
+ * (maybe_switch_prio), the new one waits for the old one once. */
+void NativeTransport::flush_reduce()
+{
+    while (!pend_reduce_.empty()) {
+        ReduceSeg segs[MPIX_PULL_BATCH];
+        size_t n = pend_reduce_.size();
+        if (n > MPIX_PULL_BATCH) n = MPIX_PULL_BATCH;
+        for (size_t i = 0; i < n; i++) {
+            const PendingReduce &pr = pend_reduce_[i];
+            segs[i] = ReduceSeg{pr.pp.dst, pr.pp.csrc, pr.pp.n, pr.type,
+                                pr.op};
+        }
+        n = plan_reduce(segs, n, MPIX_REDUCE_TILE, &rplan_);
+        uint64_t total = 0;
+        std::vector<PendingPull> items;
+        for (size_t i = 0; i < n; i++) {
+            total += pend_reduce_[i].pp.n;
+            items.push_back(pend_reduce_[i].pp);
+        }
+        pend_reduce_.erase(pend_reduce_.begin(), pend_reduce_.begin() + n);
+        hipStream_t cs = copy_stream(0);
+        if (reduce_cs_ != nullptr && reduce_cs_ != cs) {
+            hipEvent_t ev = get_event();
+            if (hipEventRecord(ev, reduce_cs_) != hipSuccess ||
+                hipStreamWaitEvent(cs, ev, 0) != hipSuccess)
+                MPIX_ERR("reduce: ordering behind the retired copy stream "
+                         "failed: %s", hipGetErrorString(hipGetLastError()));
+            put_event(ev);
+        }
+        reduce_cs_ = cs;
+        const uint64_t tiles = reduce_total_tiles(rplan_);
+        const unsigned blocks = tiles < pull_max_blocks() ? (unsigned)tiles
+                                                          : pull_max_blocks();
+        g_state->reduce_launches++;
+        g_state->reduce_msgs += pull_ops(items);
+        g_state->reduce_entries += rplan_.n;
+        /* t_launch_ns stays 0: the batch legs of MPIX_STATS count plain
+         * pulls */
+        if (submit_batch(std::move(items), cs, "k_pull_reduce",
+                         [&](const PullDone *done) {
+                             launch_reduce(rplan_, blocks, cs, done);
+                             return hipGetLastError();
+                         }) == nullptr)
+            continue;
+        if (trace_on())
+            fprintf(stderr, "[mpix trace] reduce pull batch n=%zu entries=%u "
+                    "tiles=%lu total=%lu B\n", n, rplan_.n,
+                    (unsigned long)tiles, (unsigned long)total);
     }
 }
 

@@ -1,14 +1,16 @@
 /* mpix — the pull kernels of the native transport and their launch dispatch.
  * HIP only; included by native.cpp, and by
  * tests/native/pull_kernels_check.hip, which launches every variant in here
- * directly.  The host plans a batch (pull_plan.h, strided_plan.h); what runs
- * on the device is in here. */
+ * directly (tests/native/reduce_kernels_check.hip for the reduce kernels).
+ * The host plans a batch (pull_plan.h, strided_plan.h, reduce_plan.h); what
+ * runs on the device is in here. */
 #ifndef MPIX_TRANSPORT_PULL_KERNELS_H
 #define MPIX_TRANSPORT_PULL_KERNELS_H
 
 #include <hip/hip_runtime.h>
 
 #include "pull_plan.h"
+#include "reduce_plan.h"
 #include "strided_plan.h"
 
 namespace mpix {
@@ -313,6 +315,196 @@ __global__ __launch_bounds__(PULL_THREADS) void k_pull_strided_done(
     pull_signal_done(d);
 }
 
+/* Reducing pull: dst[i] = dst[i] op src[i], the combine of reduce.h, inside
+ * the pull (MPIX_Irecv_reduce_enqueue, MPIX_Precv_init_reduce).  The launch
+ * shape is k_pull_multi's: the table (reduce_plan.h) travels by value, every
+ * entry is cut into tiles of 256 threads x 4 x 16 B and blocks grid-stride
+ * over the total tile count.  Per payload byte it moves 3 bytes (remote
+ * load, local load, store) where a pull into a staging buffer and an add
+ * kernel behind it move 5.  Per full tile a thread issues its 4 remote
+ * loads (nontemporal: the message is touched once) and its 4 local loads
+ * before the first store.  Element type and op are per entry and switched
+ * on once per tile, so one kernel serves all 18 combinations and a batch
+ * may mix them.
+ *  - vector path: both addresses of the entry 16-byte aligned; the entry's
+ *    bytes % 16 tail takes element-sized accesses;
+ *  - element path: the same walk with element-sized accesses, 16 / size
+ *    rounds per tile, for an entry with a side that is element-aligned only.
+ * Elements are loaded and stored as their bit patterns (uint16/32/64_t).
+ *
+ * Why the load of dst sees the user's data: the per-XCD L2s are not coherent
+ * with each other, so a line the user wrote on one XCD could be stale in the
+ * L2 of the XCD this block runs on.  But the user's writes finished in an
+ * EARLIER kernel (or copy) on the stream that triggered the receive, or
+ * before MPIX_Start: the end of that kernel wrote its dirty lines back to
+ * memory, and the start of this kernel invalidates what the L2s hold of
+ * them, so a plain load here is served from memory or from a line loaded
+ * after that.  The same argument covers two reducing launches behind each
+ * other on the copy stream (overlapping destinations, reduce_plan.h): the
+ * first one's end writes back (its write-through stores are in memory even
+ * sooner), the second one's start invalidates.  Inside one launch no
+ * element is touched by two blocks: plan_reduce ends the batch first.
+ *
+ * k_pull_reduce stores nontemporal and signals nothing (event and tail
+ * modes).  k_pull_reduce_done stores EVERY payload byte write-through (sc1):
+ * the full tiles, the partial tile, the tail elements and the whole element
+ * path, then pull_signal_done, with no fence, like the other _done kernels. */
+template <int BYTES> struct RedBits;
+template <> struct RedBits<2> { typedef uint16_t U; };
+template <> struct RedBits<4> { typedef uint32_t U; };
+template <> struct RedBits<8> { typedef uint64_t U; };
+
+template <int TYPE>
+using RedB = typename RedBits<sizeof(typename Red<TYPE>::T)>::U;
+
+template <int TYPE, int OP>
+static __device__ __forceinline__ RedB<TYPE> reduce_bits(RedB<TYPE> a,
+                                                         RedB<TYPE> b)
+{
+    typedef typename Red<TYPE>::T T;
+    T ta, tb;
+    __builtin_memcpy(&ta, &a, sizeof(T));
+    __builtin_memcpy(&tb, &b, sizeof(T));
+    ta = Red<TYPE>::combine(OP, ta, tb);
+    __builtin_memcpy(&a, &ta, sizeof(T));
+    return a;
+}
+
+template <int TYPE, int OP>
+static __device__ __forceinline__ pull_v4 reduce_v4(pull_v4 a, pull_v4 b)
+{
+    typedef typename Red<TYPE>::T T;
+    constexpr int PER = 16 / (int)sizeof(T);
+    T ta[PER], tb[PER];
+    __builtin_memcpy(ta, &a, 16);
+    __builtin_memcpy(tb, &b, 16);
+#pragma unroll
+    for (int i = 0; i < PER; i++) ta[i] = Red<TYPE>::combine(OP, ta[i], tb[i]);
+    __builtin_memcpy(&a, ta, 16);
+    return a;
+}
+
+/* the tile of entry `cur` that starts `off` bytes into it */
+template <int TYPE, int OP, PullStore S>
+static __device__ __forceinline__ void reduce_tile(const ReduceEntry &cur,
+                                                   uint64_t off)
+{
+    typedef RedB<TYPE> B;
+    typedef const __attribute__((address_space(1))) B *gbsrc;
+    typedef __attribute__((address_space(1))) B *gbdst;
+    constexpr int U = MPIX_REDUCE_UNROLL;
+    constexpr uint64_t TILE = MPIX_REDUCE_TILE;
+    static_assert(TILE == (uint64_t)PULL_THREADS * U * 16, "tile of the plan");
+    const uint64_t left = cur.bytes - off;
+    if (((((uintptr_t)cur.src) | ((uintptr_t)cur.dst)) & 15) == 0) {
+        pull_gsrc s = (pull_gsrc)(cur.src + off);
+        pull_gdst d = (pull_gdst)(cur.dst + off);
+        if (left >= TILE) {
+            pull_v4 a[U], b[U];
+#pragma unroll
+            for (int k = 0; k < U; k++)
+                b[k] = __builtin_nontemporal_load(s + threadIdx.x +
+                                                  k * PULL_THREADS);
+#pragma unroll
+            for (int k = 0; k < U; k++)
+                a[k] = d[threadIdx.x + k * PULL_THREADS];
+#pragma unroll
+            for (int k = 0; k < U; k++)
+                pull_st<S>(d + threadIdx.x + k * PULL_THREADS,
+                           reduce_v4<TYPE, OP>(a[k], b[k]));
+            return;
+        }
+        const uint32_t nv = (uint32_t)(left / 16);
+        for (uint32_t v = threadIdx.x; v < nv; v += PULL_THREADS)
+            pull_st<S>(d + v, reduce_v4<TYPE, OP>(
+                                  d[v], __builtin_nontemporal_load(s + v)));
+        /* bytes % 16 of the entry: whole elements, fewer than 16 / size */
+        if (threadIdx.x < (uint32_t)(left & 15) / sizeof(B)) {
+            gbsrc ts = (gbsrc)(s + nv) + threadIdx.x;
+            gbdst td = (gbdst)(d + nv) + threadIdx.x;
+            pull_st_any<S, B, true>(
+                td, reduce_bits<TYPE, OP>(*td,
+                                          __builtin_nontemporal_load(ts)));
+        }
+        return;
+    }
+    /* element path: the elements of this tile, in rounds of U x 256 */
+    gbsrc s = (gbsrc)(cur.src + off);
+    gbdst d = (gbdst)(cur.dst + off);
+    const uint32_t cnt =
+        (uint32_t)((left < TILE ? left : TILE) / sizeof(B));
+#pragma unroll 1
+    for (uint32_t j = 0; j < 16 / sizeof(B); j++) {
+        B a[U], b[U];
+        bool ok[U];
+#pragma unroll
+        for (int k = 0; k < U; k++) {
+            const uint32_t i = (j * U + k) * PULL_THREADS + threadIdx.x;
+            ok[k] = i < cnt;
+            if (ok[k]) b[k] = __builtin_nontemporal_load(s + i);
+        }
+#pragma unroll
+        for (int k = 0; k < U; k++) {
+            const uint32_t i = (j * U + k) * PULL_THREADS + threadIdx.x;
+            if (ok[k]) a[k] = d[i];
+        }
+#pragma unroll
+        for (int k = 0; k < U; k++) {
+            const uint32_t i = (j * U + k) * PULL_THREADS + threadIdx.x;
+            if (ok[k])
+                pull_st_any<S, B, true>(d + i,
+                                        reduce_bits<TYPE, OP>(a[k], b[k]));
+        }
+    }
+}
+
+template <PullStore S>
+static __device__ __forceinline__ void pull_reduce_body(const ReduceTable &t)
+{
+    const uint64_t total = t.tile_end[t.n - 1];
+    uint32_t c = 0;
+    uint64_t first = 0, end = t.tile_end[0];
+    ReduceEntry cur = t.e[0];
+    for (uint64_t tile = blockIdx.x; tile < total; tile += gridDim.x) {
+        if (tile >= end) {
+            do {
+                first = end;
+                end = t.tile_end[++c];
+            } while (tile >= end);
+            cur = t.e[c];
+        }
+        const uint64_t off = (tile - first) * MPIX_REDUCE_TILE;
+#define REDUCE_CASE(TY)                                                      \
+    case TY * RED_NOPS + RED_SUM: reduce_tile<TY, RED_SUM, S>(cur, off); break; \
+    case TY * RED_NOPS + RED_MAX: reduce_tile<TY, RED_MAX, S>(cur, off); break; \
+    case TY * RED_NOPS + RED_MIN: reduce_tile<TY, RED_MIN, S>(cur, off); break;
+        switch (cur.type * RED_NOPS + cur.op) {
+            REDUCE_CASE(RED_F32)
+            REDUCE_CASE(RED_F64)
+            REDUCE_CASE(RED_BF16)
+            REDUCE_CASE(RED_F16)
+            REDUCE_CASE(RED_I32)
+            REDUCE_CASE(RED_I64)
+        default: break; /* the host validated type and op */
+        }
+#undef REDUCE_CASE
+    }
+}
+
+__global__ __launch_bounds__(PULL_THREADS) void k_pull_reduce(
+    const ReduceTable t)
+{
+    pull_reduce_body<PULL_ST_NT>(t);
+}
+
+/* MPIX_PULL_DONE=word: write-through stores, then pull_signal_done */
+__global__ __launch_bounds__(PULL_THREADS) void k_pull_reduce_done(
+    const ReduceTable t, const PullDone d)
+{
+    pull_reduce_body<PULL_ST_WT>(t);
+    pull_signal_done(d);
+}
+
 /* Launch dispatch.  Each variant comes as a pair: the kernel that stores
  * write-through and signals the completion word, launched when `done` is
  * given, and the plain one whose completion is an event or a tail kernel
@@ -362,6 +554,19 @@ static inline void launch_strided(const StridedTable &t, bool wide, bool parts,
     else
         hipLaunchKernelGGL(k.by_event, dim3(blocks), dim3(PULL_THREADS), 0, cs,
                            t);
+}
+
+/* the reducing pull: k_pull_reduce_done when `done` is given, else
+ * k_pull_reduce */
+static inline void launch_reduce(const ReduceTable &t, unsigned blocks,
+                                 hipStream_t cs, const PullDone *done)
+{
+    if (done != nullptr)
+        hipLaunchKernelGGL(k_pull_reduce_done, dim3(blocks),
+                           dim3(PULL_THREADS), 0, cs, t, *done);
+    else
+        hipLaunchKernelGGL(k_pull_reduce, dim3(blocks), dim3(PULL_THREADS), 0,
+                           cs, t);
 }
 
 #undef PULL_KERNELS
