@@ -62,8 +62,10 @@ if [ "$MODE" = full ]; then
     note waitall_wave_kernel
     # single-wave waitall kernel under the kernel fallback: the r01 in-situ
     # hang was the stream->HSA-queue aliasing deadlock (see add_flag_node);
-    # with the transport copy stream on its own queue this should pass
-    MPIX_WAITALL_KERNEL=1 MPIX_DISABLE_MEMOPS=1 timeout 120 \
+    # with the transport copy stream on its own queue this should pass.
+    # MPIX_FAST_WAIT=0: only classic requests reach the wave kernel, a fast
+    # request is rerouted to its GTE wait
+    MPIX_FAST_WAIT=0 MPIX_WAITALL_KERNEL=1 MPIX_DISABLE_MEMOPS=1 timeout 120 \
         python -m pytest tests/test_gpu.py -q -m gpu -k "waitall or loopback" \
         > gpurun_out/waitall_wave.log 2>&1 \
         && echo OK || { echo "FAIL rc=$?"; tail -4 gpurun_out/waitall_wave.log; }

@@ -17,6 +17,8 @@
  */
 #include <hip/hip_runtime.h>
 
+#include <algorithm>
+
 #include "internal.h"
 #include "transport/layout.h"
 #include "transport/reduce.h"
@@ -89,6 +91,68 @@ __global__ void k_waitall_and_set(uint32_t *flags, const int32_t *idx,
 static inline void mark_spin_wait()
 {
     g_state->spin_wait_kernels.store(true, std::memory_order_release);
+}
+
+/* MPIX_STATS=1: one more trigger or wait of the kind `c` (see State) */
+static inline void stat_add(std::atomic<uint64_t> &c, uint64_t n = 1)
+{
+    if (g_state->stats) c.fetch_add(n, std::memory_order_relaxed);
+}
+
+/* Pinned index arrays of the waitall wave kernel.  The stream hands an array
+ * back from a host function, which may make no HIP call (hipLaunchHostFunc),
+ * so arrays are never freed from there: they return to this list and the
+ * next waitall takes one that is large enough.  Process-wide and leaked on
+ * purpose, like lifecycle_mutex(): a host function can run after
+ * MPIX_Finalize. */
+struct IdxBuf {
+    int32_t *host = nullptr;
+    int32_t *dev = nullptr;
+    int cap = 0;
+};
+struct IdxPool {
+    std::mutex m;
+    std::vector<IdxBuf *> free;
+};
+static IdxPool &idx_pool()
+{
+    static IdxPool *p = new IdxPool();
+    return *p;
+}
+
+static IdxBuf *idx_buf_get(int count)
+{
+    IdxPool &pool = idx_pool();
+    {
+        std::lock_guard<std::mutex> lk(pool.m);
+        for (size_t i = 0; i < pool.free.size(); i++) {
+            if (pool.free[i]->cap < count) continue;
+            IdxBuf *b = pool.free[i];
+            pool.free[i] = pool.free.back();
+            pool.free.pop_back();
+            return b;
+        }
+    }
+    IdxBuf *b = new IdxBuf();
+    b->cap = count < 64 ? 64 : count;
+    if (hipHostMalloc((void **)&b->host, (size_t)b->cap * sizeof(int32_t),
+                      hipHostMallocMapped) != hipSuccess ||
+        hipHostGetDevicePointer((void **)&b->dev, b->host, 0) != hipSuccess) {
+        (void)hipGetLastError();
+        MPIX_ERR("pinned index array for %d flags: allocation failed", count);
+        if (b->host) (void)hipHostFree(b->host);
+        delete b;
+        return nullptr;
+    }
+    return b;
+}
+
+/* also the host function behind the wave kernel: no HIP call in here */
+static void idx_buf_put(void *p)
+{
+    IdxPool &pool = idx_pool();
+    std::lock_guard<std::mutex> lk(pool.m);
+    pool.free.push_back((IdxBuf *)p);
 }
 
 static bool stream_capturing(hipStream_t stream)
@@ -252,10 +316,12 @@ static int fire_trigger(int idx, int qtype, void *queue, Request *req)
         if (s->use_capture_memops) {
             MPIX_CHECK_HIP(hipStreamWriteValue32(
                 stream, flag_d, (uint32_t)MPIX_FLAG_PENDING, 0));
+            stat_add(s->trig_memop_capture);
         } else {
             hipLaunchKernelGGL(k_set_flag, dim3(1), dim3(1), 0, stream,
                                flag_d, (uint32_t)MPIX_FLAG_PENDING);
             MPIX_CHECK_HIP(hipGetLastError());
+            stat_add(s->trig_kernel_capture);
         }
         /* request lifetime follows the captured graph */
         hipStreamCaptureStatus cst;
@@ -270,10 +336,12 @@ static int fire_trigger(int idx, int qtype, void *queue, Request *req)
     if (s->use_memops) {
         MPIX_CHECK_HIP(hipStreamWriteValue32(stream, flag_d,
                                              (uint32_t)MPIX_FLAG_PENDING, 0));
+        stat_add(s->trig_memop_stream);
     } else {
         hipLaunchKernelGGL(k_set_flag, dim3(1), dim3(1), 0, stream, flag_d,
                            (uint32_t)MPIX_FLAG_PENDING);
         MPIX_CHECK_HIP(hipGetLastError());
+        stat_add(s->trig_kernel_stream);
     }
     return MPI_SUCCESS;
 }
@@ -485,6 +553,7 @@ static bool try_complete_now(int idx, MPI_Status *status)
         if (status != nullptr && status != MPI_STATUS_IGNORE)
             *status = op->saved_status;
         flag_store(idx, MPIX_FLAG_CLEANUP);
+        stat_add(s->wait_consumed);
         return true;
     }
     if (status != nullptr && status != MPI_STATUS_IGNORE)
@@ -525,6 +594,7 @@ extern "C" int MPIX_Wait_enqueue(MPIX_Request *reqp, MPI_Status *status,
                     *status = req->fast_status;
                 delete req;
                 *reqp = MPIX_REQUEST_NULL;
+                stat_add(s->wait_consumed);
                 return MPI_SUCCESS;
             }
             /* copy everything we need BEFORE publishing consume=1: once the
@@ -540,11 +610,13 @@ extern "C" int MPIX_Wait_enqueue(MPIX_Request *reqp, MPI_Status *status,
             MPIX_CHECK_HIP(hipStreamWaitValue32(stream, seq_d, wait_seq,
                                                 hipStreamWaitValueGte,
                                                 0xFFFFFFFFu));
+            stat_add(s->wait_gte);
         } else {
             mark_spin_wait();
             hipLaunchKernelGGL(k_wait_flag_gte, dim3(1), dim3(1), 0, stream,
                                seq_d, wait_seq);
             MPIX_CHECK_HIP(hipGetLastError());
+            stat_add(s->wait_k_gte);
         }
         *reqp = MPIX_REQUEST_NULL;
         return MPI_SUCCESS;
@@ -593,11 +665,13 @@ extern "C" int MPIX_Wait_enqueue(MPIX_Request *reqp, MPI_Status *status,
                                                 (uint32_t)MPIX_FLAG_COMPLETED,
                                                 hipStreamWaitValueEq,
                                                 0xFFFFFFFFu));
+            stat_add(s->wait_capture_memop);
         } else {
             mark_spin_wait();
             hipLaunchKernelGGL(k_wait_flag, dim3(1), dim3(1), 0, stream,
                                flag_d, (uint32_t)MPIX_FLAG_COMPLETED);
             MPIX_CHECK_HIP(hipGetLastError());
+            stat_add(s->wait_k_flag);
         }
         *reqp = MPIX_REQUEST_NULL;
         return MPI_SUCCESS;
@@ -613,12 +687,14 @@ extern "C" int MPIX_Wait_enqueue(MPIX_Request *reqp, MPI_Status *status,
                                             hipStreamWaitValueEq, 0xFFFFFFFFu));
         MPIX_CHECK_HIP(hipStreamWriteValue32(stream, flag_d,
                                              (uint32_t)MPIX_FLAG_CLEANUP, 0));
+        stat_add(s->wait_eq_pairs);
     } else {
         mark_spin_wait();
         hipLaunchKernelGGL(k_wait_and_set, dim3(1), dim3(1), 0, stream,
                            flag_d, (uint32_t)MPIX_FLAG_COMPLETED,
                            (uint32_t)MPIX_FLAG_CLEANUP);
         MPIX_CHECK_HIP(hipGetLastError());
+        stat_add(s->wait_k_and_set);
     }
     *reqp = MPIX_REQUEST_NULL;
     return MPI_SUCCESS;
@@ -681,8 +757,21 @@ extern "C" int MPIX_Waitall_enqueue(int count, MPIX_Request *reqs,
 
     /* batched memOps fast path: one submission for all waits+cleanups */
     if (!capturing && s->use_batch_memops) {
+        /* hipStreamBatchMemOp takes fewer than 256 operations: a waitall
+         * over more requests goes out as several submissions of whole
+         * (wait, write) pairs, in order on the stream */
+        constexpr size_t BATCH_MAX_OPS = 254;
         std::vector<hipStreamBatchMemOpParams> params;
-        params.reserve(2 * (size_t)count);
+        params.reserve(std::min(2 * (size_t)count, BATCH_MAX_OPS));
+        auto submit = [&]() -> int {
+            if (params.empty()) return MPI_SUCCESS;
+            MPIX_CHECK_HIP(hipStreamBatchMemOp(stream,
+                                               (unsigned)params.size(),
+                                               params.data(), 0));
+            stat_add(s->wait_eq_pairs, params.size() / 2);
+            params.clear();
+            return MPI_SUCCESS;
+        };
         for (int i = 0; i < count; i++) {
             Request *req = (Request *)reqs[i];
             if (req == nullptr) continue;
@@ -716,11 +805,9 @@ extern "C" int MPIX_Waitall_enqueue(int count, MPIX_Request *reqs,
             wr.writeValue.value = MPIX_FLAG_CLEANUP;
             params.push_back(wr);
             reqs[i] = MPIX_REQUEST_NULL;
+            if (params.size() >= BATCH_MAX_OPS) MPIX_CHECK(submit());
         }
-        if (!params.empty())
-            MPIX_CHECK_HIP(hipStreamBatchMemOp(stream,
-                                               (unsigned)params.size(),
-                                               params.data(), 0));
+        MPIX_CHECK(submit());
         return MPI_SUCCESS;
     }
 
@@ -747,6 +834,7 @@ extern "C" int MPIX_Waitall_enqueue(int count, MPIX_Request *reqs,
                     hipStreamWaitValueEq, 0xFFFFFFFFu));
                 MPIX_CHECK_HIP(hipStreamWriteValue32(
                     stream, flag_d, (uint32_t)MPIX_FLAG_CLEANUP, 0));
+                stat_add(s->wait_eq_pairs);
             }
             reqs[i] = MPIX_REQUEST_NULL;
         }
@@ -777,12 +865,14 @@ extern "C" int MPIX_Waitall_enqueue(int count, MPIX_Request *reqs,
                 MPIX_CHECK_HIP(hipStreamWaitValue32(
                     stream, s->flags_d + idx, (uint32_t)MPIX_FLAG_COMPLETED,
                     hipStreamWaitValueEq, 0xFFFFFFFFu));
+                stat_add(s->wait_capture_memop);
             } else {
                 mark_spin_wait();
-            hipLaunchKernelGGL(k_wait_flag, dim3(1), dim3(1), 0, stream,
+                hipLaunchKernelGGL(k_wait_flag, dim3(1), dim3(1), 0, stream,
                                    s->flags_d + idx,
                                    (uint32_t)MPIX_FLAG_COMPLETED);
                 MPIX_CHECK_HIP(hipGetLastError());
+                stat_add(s->wait_k_flag);
             }
             reqs[i] = MPIX_REQUEST_NULL;
         }
@@ -792,8 +882,9 @@ extern "C" int MPIX_Waitall_enqueue(int count, MPIX_Request *reqs,
     /* kernel fallback (no memOps, not capturing).  The single-wave variant
      * (k_waitall_and_set: one launch polls every flag) is the default for
      * 4+ requests — its r01 "in-situ hang" was the shared-hardware-queue
-     * blocking class (see add_flag_node), fixed by the copy-stream design;
-     * the forced-mode gpu_ci stage (waitall_wave_kernel) keeps it covered.
+     * blocking class (see add_flag_node), fixed by the copy-stream design.
+     * tests/test_wait_modes_gpu.py runs both variants (classic requests
+     * only: a fast request is rerouted and never reaches these kernels).
      * MPIX_WAITALL_KERNEL=0 forces per-request k_wait_and_set launches,
      * =1 forces the wave kernel even for small counts. */
     static const int wave_env = [] {
@@ -816,29 +907,28 @@ extern "C" int MPIX_Waitall_enqueue(int count, MPIX_Request *reqs,
             }
             if (!try_complete_now(idx, status_at(i))) {
                 mark_spin_wait();
-            hipLaunchKernelGGL(k_wait_and_set, dim3(1), dim3(1), 0,
+                hipLaunchKernelGGL(k_wait_and_set, dim3(1), dim3(1), 0,
                                    stream, s->flags_d + idx,
                                    (uint32_t)MPIX_FLAG_COMPLETED,
                                    (uint32_t)MPIX_FLAG_CLEANUP);
                 MPIX_CHECK_HIP(hipGetLastError());
+                stat_add(s->wait_k_and_set);
             }
             reqs[i] = MPIX_REQUEST_NULL;
         }
         return MPI_SUCCESS;
     }
 
-    /* single-wave path: one launch polls every flag.
-     * The index array rides in pinned memory freed by a host callback. */
-    int32_t *idx_arr = nullptr;
-    MPIX_CHECK_HIP(hipHostMalloc((void **)&idx_arr,
-                                 (size_t)count * sizeof(int32_t),
-                                 hipHostMallocMapped));
+    /* single-wave path: one launch polls every flag.  The index array is
+     * pinned memory that a host function behind the kernel hands back. */
+    IdxBuf *ib = idx_buf_get(count);
+    if (ib == nullptr) return MPI_ERR_OTHER;
     int n = 0;
     for (int i = 0; i < count; i++) {
         Request *req = (Request *)reqs[i];
         if (req == nullptr) continue;
         if (req->kind != ReqKind::BASIC) {
-            (void)hipHostFree(idx_arr);
+            idx_buf_put(ib);
             return MPI_ERR_REQUEST;
         }
         if (req->fast) { /* same rerouting as the other Waitall branches */
@@ -846,7 +936,7 @@ extern "C" int MPIX_Waitall_enqueue(int count, MPIX_Request *reqs,
             int rc = MPIX_Wait_enqueue(&r1, status_at(i),
                                        MPIX_QUEUE_HIP_STREAM, queue);
             if (rc != MPI_SUCCESS) {
-                (void)hipHostFree(idx_arr);
+                idx_buf_put(ib);
                 return rc;
             }
             reqs[i] = MPIX_REQUEST_NULL;
@@ -856,25 +946,33 @@ extern "C" int MPIX_Waitall_enqueue(int count, MPIX_Request *reqs,
         if (try_complete_now(idx, status_at(i))) {
             /* done already */
         } else {
-            idx_arr[n++] = idx;
+            ib->host[n++] = idx;
         }
         reqs[i] = MPIX_REQUEST_NULL;
     }
     if (n > 0) {
-        int32_t *idx_d = nullptr;
-        MPIX_CHECK_HIP(hipHostGetDevicePointer((void **)&idx_d, idx_arr, 0));
         int threads = n < 64 ? 64 : ((n + 63) / 64) * 64;
         if (threads > 1024) threads = 1024;
         mark_spin_wait();
-            hipLaunchKernelGGL(k_waitall_and_set, dim3(1), dim3(threads), 0,
-                           stream, s->flags_d, idx_d, n,
+        hipLaunchKernelGGL(k_waitall_and_set, dim3(1), dim3(threads), 0,
+                           stream, s->flags_d, ib->dev, n,
                            (uint32_t)MPIX_FLAG_COMPLETED,
                            (uint32_t)MPIX_FLAG_CLEANUP);
         MPIX_CHECK_HIP(hipGetLastError());
-        MPIX_CHECK_HIP(hipLaunchHostFunc(
-            stream, [](void *p) { (void)hipHostFree(p); }, idx_arr));
+        if (s->stats) {
+            s->wave_launches.fetch_add(1, std::memory_order_relaxed);
+            s->wave_flags.fetch_add((uint64_t)n, std::memory_order_relaxed);
+            if ((uint64_t)n >
+                s->wave_max_flags.load(std::memory_order_relaxed)) {
+                s->wave_max_flags.store((uint64_t)n,
+                                        std::memory_order_relaxed);
+                s->wave_max_threads.store((uint64_t)threads,
+                                          std::memory_order_relaxed);
+            }
+        }
+        MPIX_CHECK_HIP(hipLaunchHostFunc(stream, idx_buf_put, ib));
     } else {
-        (void)hipHostFree(idx_arr);
+        idx_buf_put(ib);
     }
     return MPI_SUCCESS;
 }

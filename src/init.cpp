@@ -744,6 +744,31 @@ extern "C" int MPIX_Finalize(void)
                     rn ? (double)s->reset_ns.load() / 1e3 / (double)rn : 0.0,
                     (double)s->reset_max_ns.load() / 1e3);
         }
+        /* which path each trigger and each stream wait took (enqueue.cpp) */
+        fprintf(stderr,
+                "[mpix stats r%d] triggers: stream memOp %lu, stream "
+                "k_set_flag %lu, capture memOp %lu, capture k_set_flag %lu\n",
+                s->world_rank, (unsigned long)s->trig_memop_stream.load(),
+                (unsigned long)s->trig_kernel_stream.load(),
+                (unsigned long)s->trig_memop_capture.load(),
+                (unsigned long)s->trig_kernel_capture.load());
+        fprintf(stderr,
+                "[mpix stats r%d] stream waits: WaitValueEq+CLEANUP %lu, "
+                "WaitValueGte %lu, capture WaitValueEq %lu, k_wait_flag "
+                "(capture) %lu, k_wait_flag_gte %lu, k_wait_and_set %lu, "
+                "k_waitall_and_set %lu launches for %lu flags (largest %lu "
+                "flags on %lu threads), consumed at enqueue %lu\n",
+                s->world_rank, (unsigned long)s->wait_eq_pairs.load(),
+                (unsigned long)s->wait_gte.load(),
+                (unsigned long)s->wait_capture_memop.load(),
+                (unsigned long)s->wait_k_flag.load(),
+                (unsigned long)s->wait_k_gte.load(),
+                (unsigned long)s->wait_k_and_set.load(),
+                (unsigned long)s->wave_launches.load(),
+                (unsigned long)s->wave_flags.load(),
+                (unsigned long)s->wave_max_flags.load(),
+                (unsigned long)s->wave_max_threads.load(),
+                (unsigned long)s->wait_consumed.load());
     }
 
     if (s->t_native) {

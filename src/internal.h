@@ -416,6 +416,24 @@ struct State {
     std::atomic<uint64_t> start_ns{0}, start_max_ns{0}, start_n{0};
     std::atomic<uint64_t> reset_ns{0}, reset_max_ns{0}, reset_n{0};
     std::atomic<uint64_t> arm_pushes{0};
+    /* which path each trigger and each stream wait took (enqueue.cpp),
+     * counted only with MPIX_STATS=1 by the enqueuing threads.  Triggers:
+     * hipStreamWriteValue32 or a k_set_flag launch, on a stream or recorded
+     * into a capture. */
+    std::atomic<uint64_t> trig_memop_stream{0}, trig_kernel_stream{0};
+    std::atomic<uint64_t> trig_memop_capture{0}, trig_kernel_capture{0};
+    /* waits, one per request: the classic WaitValueEq + CLEANUP write pair
+     * (single or in a batch), the fast WaitValueGte, the poll-only waits of
+     * a capture (memOp or k_wait_flag), the fallback kernels, and requests
+     * that were complete at enqueue and got no stream work */
+    std::atomic<uint64_t> wait_eq_pairs{0}, wait_gte{0};
+    std::atomic<uint64_t> wait_capture_memop{0}, wait_k_flag{0};
+    std::atomic<uint64_t> wait_k_gte{0}, wait_k_and_set{0};
+    std::atomic<uint64_t> wait_consumed{0};
+    /* k_waitall_and_set: launches, the flags they polled in all, and the
+     * launch with the most flags: its flags and its threads */
+    std::atomic<uint64_t> wave_launches{0}, wave_flags{0};
+    std::atomic<uint64_t> wave_max_flags{0}, wave_max_threads{0};
     /* MPIX_PULL_DONE=word, tail: batches whose word was seen, and
      * for them the time until the event recorded behind the same kernel(s)
      * was seen too; the mode's name as it was given */

@@ -1,6 +1,9 @@
 """MPIX_FAST_WAIT=1 tier: the epoch/GTE wait protocol (single-memOp waits,
-slots recycled at completion).  Runs the protocol-critical subset in fast
-mode so both state machines stay covered by default CI."""
+slots recycled at completion).  Fast-wait is the default, so this file runs
+the protocol-critical subset under the same state machine as the rest of
+the suite, with the switch set explicitly; the classic EQ protocol
+(MPIX_FAST_WAIT=0) is covered by tests/test_classic_wait.py on the host
+path and by tests/test_wait_modes_gpu.py on the stream path."""
 import os
 
 import numpy as np
