@@ -43,9 +43,9 @@ src/transport/native.o: src/transport/pull_plan.h src/transport/layout.h \
                         src/transport/strided_plan.h src/transport/part_run.h \
                         src/transport/done_ring.h src/transport/pull_kernels.h \
                         src/transport/shm_ring.h src/transport/reduce.h \
-                        src/transport/reduce_plan.h
-src/enqueue.o src/partitioned.o: src/transport/layout.h
-src/enqueue.o: src/transport/reduce.h
+                        src/transport/reduce_plan.h \
+                        src/transport/strided_reduce_plan.h
+src/enqueue.o src/partitioned.o: src/transport/layout.h src/transport/reduce.h
 
 $(LIB): $(OBJS)
 	$(HIPCC) --offload-arch=$(GPU_ARCH) $(OBJS) $(LDFLAGS) -o $@
@@ -78,4 +78,15 @@ reduce_check:
 reduce_kernels_check:
 	$(MAKE) -C tools bin/reduce_kernels_check
 
-.PHONY: all clean python mpi4check reduce_check reduce_kernels_check
+# The same for the strided reducing receive: strided_reduce_plan.h and
+# layout_reduce_in on the CPU, the strided reduce kernels on a GPU
+# (tests/test_strided_reduce_ref.py, tests/test_strided_reduce_kernels_gpu.py).
+strided_reduce_check:
+	$(MAKE) -C tools bin/strided_reduce_check
+	tools/bin/strided_reduce_check
+
+strided_reduce_kernels_check:
+	$(MAKE) -C tools bin/strided_reduce_kernels_check
+
+.PHONY: all clean python mpi4check reduce_check reduce_kernels_check \
+        strided_reduce_check strided_reduce_kernels_check

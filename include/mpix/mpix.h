@@ -141,15 +141,49 @@ int MPIX_Irecv_strided_enqueue(void *buf, const MPIX_Layout *layout,
  * buffer (the elements that fit are combined); MPI_ERR_TYPE, the buffer
  * untouched, when the message length is not a multiple of the element size,
  * a device sender's source address is not element-aligned, the sender's
- * message is strided, or one side is in host memory and the other in device
- * memory (a device receive that gets host chunks included).
- * Not supported: reducing strided receives, user-defined ops. */
+ * message is strided (for MPIX_Irecv_reduce_enqueue and
+ * MPIX_Precv_init_reduce; the strided reducing calls below accept one), or
+ * one side is in host memory and the other in device memory (a device
+ * receive that gets host chunks included).
+ * Not supported: user-defined ops.  Reducing into a strided buffer, or from
+ * a strided sender: MPIX_Irecv_reduce_strided_enqueue and
+ * MPIX_Precv_init_reduce_strided below. */
 enum { MPIX_F32, MPIX_F64, MPIX_BF16, MPIX_F16, MPIX_I32, MPIX_I64 };
 enum { MPIX_SUM, MPIX_MAX, MPIX_MIN };
 
 int MPIX_Irecv_reduce_enqueue(void *buf, int count, int type, int op,
                               int source, int tag, MPI_Comm comm,
                               MPIX_Request *request, int qtype, void *queue);
+
+/* Strided reducing receive: the message is combined into a buffer laid out
+ * as *layout (mpix_layout.h): the boundary face of a grid, a sub-block of a
+ * pitched matrix.  On completion every whole element i of the message, in
+ * the layout's (plane, run, byte) order, has been combined once into the
+ * buffer at the layout's offset of its position; bytes in the gaps between
+ * runs are neither read into the result nor written.  ANY sender matches,
+ * whatever the receive's own layout: contiguous or strided, the plain or the
+ * strided send calls (only the byte sequence has to agree).  Device buffers
+ * are combined inside one strided pull kernel (no staging buffer, no
+ * unpack-add kernel behind the wait), host buffers run by run as the chunks
+ * arrive.  Numeric definition, request behaviour, reuse (it accumulates
+ * again) and overlapping receives are those of MPIX_Irecv_reduce_enqueue.
+ * A zero-byte message completes with 0 bytes and no error whatever memory
+ * the two sides are in: it touches none.
+ * Errors at the call: MPI_ERR_ARG for a null or illegal layout (the rules of
+ * the strided calls), an unknown type or op, a buf not aligned to the
+ * element size, a run_bytes or a stride in use that is not a multiple of the
+ * element size; MPI_ERR_TYPE for a communicator served by the MPI
+ * passthrough.  As the completion status, with the sender still acked and
+ * completing: MPI_ERR_TRUNCATE for a longer message (the whole elements that
+ * fit are combined); MPI_ERR_TYPE, the buffer untouched, when the message
+ * length is not a multiple of the element size, when a device sender's
+ * address, run or strides in use are not multiples of the element size (an
+ * element would straddle two runs), or when one side is in host memory and
+ * the other in device memory. */
+int MPIX_Irecv_reduce_strided_enqueue(void *buf, const MPIX_Layout *layout,
+                                      int type, int op, int source, int tag,
+                                      MPI_Comm comm, MPIX_Request *request,
+                                      int qtype, void *queue);
 
 int MPIX_Wait_enqueue(MPIX_Request *req, MPI_Status *status, int qtype,
                       void *queue);
@@ -210,6 +244,22 @@ int MPIX_Precv_init_strided(void *buf, int partitions,
 int MPIX_Precv_init_reduce(void *buf, int partitions, MPI_Count count,
                            int type, int op, int source, int tag,
                            MPI_Comm comm, MPI_Info info, MPIX_Request *request);
+
+/* Strided reducing variant: partition p is the buffer at
+ * buf + p * part_stride laid out as *part_layout, and each arriving
+ * partition is combined into it (semantics and errors:
+ * MPIX_Irecv_reduce_strided_enqueue and MPIX_Precv_init_strided; with more
+ * than one partition part_stride must be a multiple of the element size
+ * too; MPI_ERR_TYPE also under MPIX_MPI_PARTITIONED=1).  The sender uses
+ * MPIX_Psend_init or MPIX_Psend_init_strided with the same bytes per
+ * partition.  Device partitions made ready together are combined by one
+ * kernel entry, folded into one layout where both sides fold and by the
+ * kernel's partition level otherwise. */
+int MPIX_Precv_init_reduce_strided(void *buf, int partitions,
+                                   const MPIX_Layout *part_layout,
+                                   int64_t part_stride, int type, int op,
+                                   int source, int tag, MPI_Comm comm,
+                                   MPI_Info info, MPIX_Request *request);
 
 /* Build a device-resident handle for __device__ MPIX_Pready/Parrived. */
 int MPIX_Prequest_create(MPIX_Request request, MPIX_Prequest *prequest);

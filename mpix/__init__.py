@@ -199,11 +199,13 @@ _REDUCE_TYPES = {"float32": _C.F32, "float64": _C.F64, "bfloat16": _C.BF16,
                  "float16": _C.F16, "int32": _C.I32, "int64": _C.I64}
 
 
-def _reduce_args(buf, op):
+def _reduce_args(buf, op, views=False):
     """(address, elements, type, op) of a reducing receive into `buf`: a
     contiguous torch tensor (float32, float64, bfloat16, float16, int32,
     int64) or numpy array (the same without bfloat16).  ValueError for any
-    other dtype, a non-contiguous view or an unknown op."""
+    other dtype, a non-contiguous view (unless `views`: the strided reducing
+    receives, which take the address and the layout from the view) or an
+    unknown op."""
     if op not in _REDUCE_OPS:
         raise ValueError(f"unknown reduce op {op!r}: one of "
                          f"{sorted(_REDUCE_OPS)}")
@@ -221,9 +223,11 @@ def _reduce_args(buf, op):
     if name not in _REDUCE_TYPES:
         raise ValueError(f"cannot reduce into dtype {name}: one of "
                          f"{sorted(_REDUCE_TYPES)}")
-    if not contiguous:
-        raise ValueError("a reducing receive needs a contiguous buffer "
-                         "(reducing strided receives are not supported)")
+    if not contiguous and not views:
+        raise ValueError("a reducing receive needs a contiguous buffer (for "
+                         "a view: irecv_reduce_strided_enqueue, "
+                         "irecv_reduce_strided_graph, "
+                         "precv_reduce_strided_init)")
     return int(addr), int(count), _REDUCE_TYPES[name], _REDUCE_OPS[op]
 
 
@@ -254,6 +258,53 @@ def precv_reduce_init(buf, partitions, source, op="sum", tag=0):
                          f"{partitions} partitions")
     return _C.precv_init_reduce(addr, partitions, count // partitions, typ,
                                 rop, source, tag)
+
+
+def _irecv_reduce_strided(buf, source, op, tag, qtype, stream):
+    _, count, typ, rop = _reduce_args(buf, op, views=True)
+    lay = _layout_of(buf)  # ValueError for what does not fit a layout
+    if lay is None:
+        addr, n = _addr_len(buf)
+        layout = (n, 1, 1, n, n)
+    else:
+        addr, layout = lay
+    return _C.irecv_reduce_strided(addr, *layout, typ, rop, source, tag,
+                                   qtype, _stream_addr(stream))
+
+
+def irecv_reduce_strided_enqueue(buf, source, op="sum", tag=0, stream=None):
+    """irecv_reduce_enqueue into `buf`, a contiguous tensor / ndarray or any
+    view irecv_enqueue accepts (see _layout_of): the message's elements are
+    combined into the view's elements in C order, and what lies between them
+    is neither read nor written.  The sender may send a contiguous buffer or
+    any view with the same number of bytes."""
+    return _irecv_reduce_strided(buf, source, op, tag, QUEUE_STREAM, stream)
+
+
+def irecv_reduce_strided_graph(buf, source, op="sum", tag=0):
+    """Graph-construction variant: returns (request, graph_handle).  Every
+    launch of the graph combines again."""
+    return _irecv_reduce_strided(buf, source, op, tag, QUEUE_GRAPH, None)
+
+
+def precv_reduce_strided_init(buf, partitions, source, op="sum", tag=0):
+    """Partitioned reducing receive into `buf`, a contiguous tensor / ndarray
+    cut into `partitions` equal slices or a view whose dimension 0 is split
+    into `partitions` equal slabs (as precv_init): each arriving partition
+    is combined into its slab.  Every iteration (start) accumulates
+    again."""
+    _, count, typ, rop = _reduce_args(buf, op, views=True)
+    if not _is_view(buf):
+        if partitions <= 0 or count % partitions != 0:
+            raise ValueError(f"{count} elements do not divide evenly into "
+                             f"{partitions} partitions")
+        addr, n = _addr_len(buf)
+        per = n // partitions
+        layout, part_stride = (per, 1, 1, per, per), per
+    else:
+        addr, layout, part_stride = _view_partitions(buf, partitions)
+    return _C.precv_init_reduce_strided(addr, partitions, *layout,
+                                        part_stride, typ, rop, source, tag)
 
 
 def waitall_graph(reqs):
@@ -309,6 +360,14 @@ def _pinit(is_send, buf, partitions, peer, tag, nbytes):
     if nbytes is not None:
         raise ValueError("nbytes= cannot be combined with a non-contiguous "
                          "buffer: the view defines the partitions")
+    addr, layout, part_stride = _view_partitions(buf, partitions)
+    return _C.psend_precv_init_strided(is_send, addr, partitions, *layout,
+                                       part_stride, peer, tag)
+
+
+def _view_partitions(buf, partitions):
+    """(address, layout, part_stride) of the `partitions` equal slabs that
+    dimension 0 of the non-contiguous view `buf` splits into."""
     shape = tuple(buf.shape)
     if hasattr(buf, "data_ptr"):
         item = buf.element_size()
@@ -338,8 +397,7 @@ def _pinit(is_send, buf, partitions, peer, tag, nbytes):
         layout = (n, 1, 1, n, n)
     else:
         layout = lay[1]
-    return _C.psend_precv_init_strided(is_send, int(addr), partitions,
-                                       *layout, int(part_stride), peer, tag)
+    return int(addr), layout, int(part_stride)
 
 
 def psend_init(buf, partitions, dest, tag=0, nbytes=None):

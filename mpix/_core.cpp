@@ -257,6 +257,39 @@ PYBIND11_MODULE(_C, m)
               return pr;
           });
 
+    /* the same into a buffer laid out as (run_bytes, count0, count1,
+     * stride0, stride1): MPIX_Irecv_reduce_strided_enqueue */
+    m.def("irecv_reduce_strided",
+          [](uintptr_t buf, uint64_t run_bytes, uint64_t count0,
+             uint64_t count1, int64_t stride0, int64_t stride1, int type,
+             int op, int source, int tag, int qtype,
+             uintptr_t stream) -> py::object {
+              MPIX_Layout l;
+              l.run_bytes = run_bytes;
+              l.count[0] = count0;
+              l.count[1] = count1;
+              l.stride[0] = stride0;
+              l.stride[1] = stride1;
+              auto *r = new MxRequest();
+              hipGraph_t g = nullptr;
+              void *q = qtype == MPIX_QUEUE_HIP_GRAPH ? (void *)&g
+                                                      : (void *)&stream;
+              int rc = MPIX_Irecv_reduce_strided_enqueue(
+                  (void *)buf, &l, type, op, source, tag, MPI_COMM_WORLD,
+                  &r->req, qtype, q);
+              if (rc != 0) {
+                  delete r;
+                  throw std::runtime_error(
+                      "MPIX_Irecv_reduce_strided_enqueue failed, rc=" +
+                      std::to_string(rc));
+              }
+              py::object pr =
+                  py::cast(r, py::return_value_policy::take_ownership);
+              if (qtype == MPIX_QUEUE_HIP_GRAPH)
+                  return py::make_tuple(pr, (uintptr_t)g);
+              return pr;
+          });
+
     m.def("wait_graph", [](MxRequest *r) {
         /* per-request wait graph (the reference's composition style in
          * test/src/ring-all-graph-construction.c uses one per request) */
@@ -370,6 +403,31 @@ PYBIND11_MODULE(_C, m)
                   delete r;
                   throw std::runtime_error(
                       "MPIX_Precv_init_reduce failed, rc=" +
+                      std::to_string(rc));
+              }
+              return r;
+          },
+          py::return_value_policy::take_ownership);
+
+    m.def("precv_init_reduce_strided",
+          [](uintptr_t buf, int partitions, uint64_t run_bytes,
+             uint64_t count0, uint64_t count1, int64_t stride0,
+             int64_t stride1, int64_t part_stride, int type, int op,
+             int source, int tag) {
+              MPIX_Layout l;
+              l.run_bytes = run_bytes;
+              l.count[0] = count0;
+              l.count[1] = count1;
+              l.stride[0] = stride0;
+              l.stride[1] = stride1;
+              auto *r = new MxRequest();
+              int rc = MPIX_Precv_init_reduce_strided(
+                  (void *)buf, partitions, &l, part_stride, type, op, source,
+                  tag, MPI_COMM_WORLD, MPI_INFO_NULL, &r->req);
+              if (rc != 0) {
+                  delete r;
+                  throw std::runtime_error(
+                      "MPIX_Precv_init_reduce_strided failed, rc=" +
                       std::to_string(rc));
               }
               return r;

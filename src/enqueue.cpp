@@ -368,10 +368,31 @@ int reduce_check_args(const RedSpec &red, const void *buf, int *esize)
     return MPI_SUCCESS;
 }
 
+int reduce_check_layout(const RedSpec &red, const void *buf,
+                        const MPIX_Layout &norm, int partitions,
+                        int64_t part_stride)
+{
+    int esize = 0;
+    int rc = reduce_check_args(red, buf, &esize);
+    if (rc != MPI_SUCCESS) return rc;
+    uint64_t bits = layout_align_bits(norm, 0);
+    if (partitions > 1) bits |= (uint64_t)part_stride;
+    if (bits % (uint64_t)esize != 0) {
+        MPIX_ERR("strided reducing receive: run %lu, strides %ld %ld%s must "
+                 "be multiples of the %d-byte element (an element would "
+                 "straddle two runs)", (unsigned long)norm.run_bytes,
+                 (long)norm.stride[0], (long)norm.stride[1],
+                 partitions > 1 ? " and the part stride" : "", esize);
+        return MPI_ERR_ARG;
+    }
+    return MPI_SUCCESS;
+}
+
 /* Common body of Isend/Irecv_enqueue and their variants.  `layout` non-null
  * (strided): count and datatype are ignored, the message is the layout's.
  * `red` non-null (reducing receive): datatype is ignored, count is in
- * elements of red->type. */
+ * elements of red->type; with a layout too (the strided reducing receive)
+ * the message is the layout's. */
 static int enqueue_sendrecv(bool is_send, void *buf, int count,
                             MPI_Datatype datatype, int peer, int tag,
                             MPI_Comm comm, MPIX_Request *request, int qtype,
@@ -401,6 +422,10 @@ static int enqueue_sendrecv(bool is_send, void *buf, int count,
             return MPI_ERR_ARG;
         }
         norm = layout_normalize(*layout);
+        if (red != nullptr) {
+            int rc = reduce_check_layout(*red, buf, norm, 1, 0);
+            if (rc != MPI_SUCCESS) return rc;
+        }
         datatype = MPI_BYTE;
         uint64_t nb = layout_bytes(norm);
         count = nb > (uint64_t)INT32_MAX ? INT32_MAX : (int)nb;
@@ -445,6 +470,7 @@ static int enqueue_sendrecv(bool is_send, void *buf, int count,
         op->reduce = true;
         op->red_type = (uint8_t)red->type;
         op->red_op = (uint8_t)red->op;
+        op->reduce_any_sender = layout != nullptr;
         op->count = op->bytes > (uint64_t)INT32_MAX ? INT32_MAX
                                                     : (int)op->bytes;
     }
@@ -536,6 +562,16 @@ extern "C" int MPIX_Irecv_strided_enqueue(void *buf, const MPIX_Layout *layout,
     if (layout == nullptr) return MPI_ERR_ARG;
     return enqueue_sendrecv(false, buf, 0, MPI_BYTE, source, tag, comm,
                             request, qtype, queue, layout);
+}
+
+extern "C" int MPIX_Irecv_reduce_strided_enqueue(
+    void *buf, const MPIX_Layout *layout, int type, int op, int source,
+    int tag, MPI_Comm comm, MPIX_Request *request, int qtype, void *queue)
+{
+    if (layout == nullptr) return MPI_ERR_ARG;
+    const RedSpec red{type, op};
+    return enqueue_sendrecv(false, buf, 0, MPI_BYTE, source, tag, comm,
+                            request, qtype, queue, layout, &red);
 }
 
 /* ----------------------------------------------------------- wait (stream) */

@@ -652,6 +652,20 @@ extern "C" int MPIX_Finalize(void)
                     (unsigned long)s->reduce_msgs,
                     (unsigned long)s->reduce_entries,
                     (unsigned long)s->run_reduce);
+        if (s->sreduce_launches)
+            fprintf(stderr,
+                    "[mpix stats r%d] strided reducing receives: %lu launches "
+                    "for %lu receives in %lu entries, %lu runs taken as one "
+                    "entry\n", s->world_rank,
+                    (unsigned long)s->sreduce_launches,
+                    (unsigned long)s->sreduce_msgs,
+                    (unsigned long)s->sreduce_entries,
+                    (unsigned long)s->run_sreduce);
+        if (s->sreduce_host)
+            fprintf(stderr,
+                    "[mpix stats r%d] strided reducing receives: %lu host "
+                    "receives combined run by run\n", s->world_rank,
+                    (unsigned long)s->sreduce_host);
         if (s->bleg_first_seen) {
             /* on its own line and in none of the means below: this launch
              * loads the code object */

@@ -150,6 +150,11 @@ struct Op {
      * transport/reduce.h; bytes is a multiple of the element size */
     bool reduce = false;
     uint8_t red_type = 0, red_op = 0;
+    /* made by MPIX_Irecv_reduce_strided_enqueue or
+     * MPIX_Precv_init_reduce_strided: a strided sender matches too, whatever
+     * the receive's own layout (`strided` and `layout` as above; runs and
+     * strides are multiples of the element size) */
+    bool reduce_any_sender = false;
     uint32_t pseq = 0;              /* partitioned iteration number */
     Request *req = nullptr;         /* owning request */
 
@@ -190,7 +195,7 @@ struct Op {
         comm = MPI_COMM_NULL; comm_id = 0; buf_is_device = false;
         native_route = true;
         strided = false; layout = MPIX_Layout{};
-        reduce = false; red_type = red_op = 0;
+        reduce = false; red_type = red_op = 0; reduce_any_sender = false;
         partition = -1; pseq = 0; req = nullptr;
         t_enq_ns = 0; t_issue_ns = 0;
         ch_done.store(0, std::memory_order_relaxed);
@@ -399,6 +404,12 @@ struct State {
      * the table entries they carried, runs taken as one reduce entry */
     uint64_t reduce_launches = 0, reduce_msgs = 0, reduce_entries = 0;
     uint64_t run_reduce = 0;
+    /* strided reducing receives: launches of the strided reduce kernel, the
+     * receives and entries they carried, runs taken as one entry; host
+     * receives combined run by run */
+    uint64_t sreduce_launches = 0, sreduce_msgs = 0, sreduce_entries = 0;
+    uint64_t run_sreduce = 0;
+    uint64_t sreduce_host = 0;
     /* event -> last SEND op of a loopback batch COMPLETED (the sends are
      * completed by the same walk, behind the receives) */
     uint64_t bleg_send_done_ns = 0, bleg_send_done_n = 0;
@@ -502,6 +513,12 @@ struct RedSpec {
 /* MPI_SUCCESS and *esize, or MPI_ERR_ARG: unknown type or op, or `buf` not
  * aligned to the element size */
 int reduce_check_args(const RedSpec &red, const void *buf, int *esize);
+/* the same for the strided reducing calls, whose normalised layout `norm`
+ * (and, with more than one partition, part_stride) must step in whole
+ * elements too */
+int reduce_check_layout(const RedSpec &red, const void *buf,
+                        const MPIX_Layout &norm, int partitions,
+                        int64_t part_stride);
 
 /* Write an MPI_Status (MPICH layout) from a transport completion. */
 void fill_status(MPI_Status *st, const ChStatus &cs);

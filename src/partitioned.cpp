@@ -28,7 +28,8 @@ namespace mpix {
  * `layout` non-null (the strided calls): count and datatype are ignored,
  * partition p is the buffer at buf + p * part_stride laid out as *layout.
  * `red` non-null (MPIX_Precv_init_reduce): datatype is ignored, count is in
- * elements of red->type. */
+ * elements of red->type; with a layout too (MPIX_Precv_init_reduce_strided)
+ * the partition is the layout's. */
 static int psend_precv_init(bool is_send, void *buf, int partitions,
                             MPI_Count count, MPI_Datatype datatype, int peer,
                             int tag, MPI_Comm comm, MPIX_Request *request,
@@ -69,6 +70,11 @@ static int psend_precv_init(bool is_send, void *buf, int partitions,
             }
         }
         norm = layout_normalize(*layout);
+        if (red != nullptr) {
+            int rc = reduce_check_layout(*red, buf, norm, partitions,
+                                         part_stride);
+            if (rc != MPI_SUCCESS) return rc;
+        }
         datatype = MPI_BYTE;
         tsz = 1;
         count = (MPI_Count)layout_bytes(norm);
@@ -189,6 +195,7 @@ static int psend_precv_init(bool is_send, void *buf, int partitions,
             op->reduce = true;
             op->red_type = (uint8_t)red->type;
             op->red_op = (uint8_t)red->op;
+            op->reduce_any_sender = layout != nullptr;
         }
         /* native shm/xGMI for WORLD/SELF; MPI transport for arbitrary comms
          * (header-routed partition messages) and the MPI-4.0 passthrough */
@@ -257,6 +264,18 @@ extern "C" int MPIX_Precv_init_strided(void *buf, int partitions,
     if (part_layout == nullptr) return MPI_ERR_ARG;
     return psend_precv_init(false, buf, partitions, 0, MPI_BYTE, source, tag,
                             comm, request, part_layout, part_stride);
+}
+
+extern "C" int MPIX_Precv_init_reduce_strided(
+    void *buf, int partitions, const MPIX_Layout *part_layout,
+    int64_t part_stride, int type, int op, int source, int tag, MPI_Comm comm,
+    MPI_Info info, MPIX_Request *request)
+{
+    (void)info;
+    if (part_layout == nullptr) return MPI_ERR_ARG;
+    const RedSpec red{type, op};
+    return psend_precv_init(false, buf, partitions, 0, MPI_BYTE, source, tag,
+                            comm, request, part_layout, part_stride, &red);
 }
 
 extern "C" int MPIX_Start(MPIX_Request *reqp)

@@ -17,6 +17,7 @@
 #include <string.h>
 
 #include "../../include/mpix/mpix_layout.h"
+#include "reduce.h"
 
 namespace mpix {
 
@@ -223,6 +224,20 @@ static inline void layout_copy_in(void *buf, const MPIX_Layout &l,
 {
     layout_for_runs(l, pos, n, [&](int64_t off, uint64_t m, uint64_t len) {
         memcpy((char *)buf + off, (const char *)src + m, len);
+    });
+}
+
+/* src COMBINED into message bytes [pos, pos + n) of laid-out host buffer
+ * `buf` (a reducing strided receive: reduce.h).  pos, n and the layout's run
+ * are multiples of the element size, so no element straddles a piece. */
+static inline void layout_reduce_in(void *buf, const MPIX_Layout &l,
+                                    uint64_t pos, const void *src, uint64_t n,
+                                    int type, int op)
+{
+    const uint32_t es = reduce_elem_size(type);
+    layout_for_runs(l, pos, n, [&](int64_t off, uint64_t m, uint64_t len) {
+        reduce_host((char *)buf + off, (const char *)src + m, len / es, type,
+                    op);
     });
 }
 

@@ -20,7 +20,11 @@
  *                 A REDUCING receive (Op::reduce) combines the message into
  *                 its buffer inside the pull: k_pull_reduce, planned by
  *                 reduce_plan.h, the combine defined by reduce.h; host
- *                 buffers combine chunk by chunk (reduce_host).
+ *                 buffers combine chunk by chunk (reduce_host).  One that is
+ *                 strided on either side (the strided reducing calls) is an
+ *                 entry of k_pull_strided_reduce, planned by
+ *                 strided_reduce_plan.h; host buffers combine run by run
+ *                 (layout_reduce_in).
  *  host data      sender stages through the shm chunk ring (64 KiB chunks,
  *                 credit-based flow control); the receiver copies chunks
  *                 straight into the posted buffer (or an unexpected-message
@@ -61,6 +65,7 @@
 #include "reduce_plan.h"
 #include "shm_ring.h"
 #include "strided_plan.h"
+#include "strided_reduce_plan.h"
 
 namespace mpix {
 
@@ -354,6 +359,19 @@ private:
     std::vector<PendingReduce> pend_reduce_;
     ReduceTable rplan_{}; /* scratch of flush_reduce; passed by value */
     hipStream_t reduce_cs_ = nullptr; /* stream of the last reduce launch */
+    hipStream_t reduce_stream();
+
+    /* reducing pulls that are strided on either side (receives made by the
+     * strided reducing calls): k_pull_strided_reduce launches of up to
+     * MPIX_STRIDED_BATCH of them, cut where destination extents overlap
+     * (strided_reduce_plan.h), on the stream of the contiguous reducing
+     * launches and behind them */
+    struct PendingStridedReduce {
+        PendingStrided ps;
+        uint32_t type, op;
+    };
+    std::vector<PendingStridedReduce> pend_sreduce_;
+    StridedReduceTable srplan_{}; /* scratch of flush_strided_reduce */
 
     /* ---- shm ---- */
     ShmGeom geom_{};
@@ -463,6 +481,7 @@ private:
     void flush_pulls();
     void flush_strided();
     void flush_reduce();
+    void flush_strided_reduce();
     void fail_kind_mismatch(InboundMsg &m);
     const char *reduce_reject(const InboundMsg &m, const void *src) const;
     void handle_desc(int src, const Desc &d, const char *stage_base);
@@ -665,6 +684,7 @@ void NativeTransport::progress()
     flush_pulls();
     flush_strided();
     flush_reduce();
+    flush_strided_reduce();
     progress_copies();
 
     /* retry queued DONE acks */
@@ -988,12 +1008,21 @@ bool NativeTransport::try_run_fast_path(int src, const Desc &d, uint32_t k)
                        d.part_stride == (int64_t)d.msg_bytes &&
                        rq->part_stride == (int64_t)d.msg_bytes;
     /* Reducing partitions (one request: all of the range or none) are taken
-     * in the plain shape only, as ONE reduce entry of k * msg_bytes.  A
-     * strided or gapped sender expands, and start_dev_copy gives every
-     * partition its status. */
-    if (op->reduce &&
-        (!plain || d.msg_bytes % reduce_elem_size(op->red_type) != 0))
-        return false;
+     * in the plain shape as ONE reduce entry of k * msg_bytes.  In any other
+     * shape those of the strided reducing call are ONE strided reduce entry
+     * (folded, or with the partition level, as below), provided the
+     * sender's side steps in whole elements; those of the plain reducing
+     * call expand, and so does everything start_dev_copy would reject: it
+     * gives every partition its status. */
+    if (op->reduce) {
+        const uint32_t esize = reduce_elem_size(op->red_type);
+        if (d.msg_bytes % esize != 0) return false;
+        if (!plain) {
+            uint64_t bits = (uint64_t)(uintptr_t)sp | (uint64_t)d.part_stride;
+            if (s_strided) bits |= layout_align_bits(d.layout, 0);
+            if (!op->reduce_any_sender || bits % esize != 0) return false;
+        }
+    }
     /* today's run, and today's rule for it: a misaligned one expands into
      * k hipMemcpyAsync (reducing: k entries on the element path) */
     if (plain && ((((uintptr_t)op->buf) | ((uintptr_t)sp)) & 15) != 0)
@@ -1006,7 +1035,7 @@ bool NativeTransport::try_run_fast_path(int src, const Desc &d, uint32_t k)
                          (uint64_t)k * d.msg_bytes, seen_ns(op, d),
                          d.partition, k};
     g_state->run_fast_msgs += k;
-    if (op->reduce) {
+    if (op->reduce && plain) {
         pend_reduce_.push_back(PendingReduce{pp, op->red_type, op->red_op});
         g_state->run_reduce++;
         return true;
@@ -1029,6 +1058,12 @@ bool NativeTransport::try_run_fast_path(int src, const Desc &d, uint32_t k)
         ps.parts = true;
         ps.s_part_stride = d.part_stride;
         ps.d_part_stride = rq->part_stride;
+    }
+    if (op->reduce) {
+        pend_sreduce_.push_back(
+            PendingStridedReduce{ps, op->red_type, op->red_op});
+        g_state->run_sreduce++;
+        return true;
     }
     (ps.parts ? g_state->run_parts : g_state->run_folded)++;
     pend_strided_.push_back(ps);
@@ -1082,20 +1117,28 @@ void NativeTransport::attach(InboundMsg &m, Op *op)
         start_dev_copy(m);
         return;
     }
-    const char *why = op->reduce ? reduce_reject(m, nullptr) : nullptr;
+    /* a zero-byte message touches no memory of either kind: a strided
+     * reducing receive takes it whatever its own buffer (a zero-byte send
+     * always travels as one empty host chunk) */
+    const bool empty_ok = op->reduce_any_sender && m.d.msg_bytes == 0;
+    const char *why =
+        op->reduce && !empty_ok ? reduce_reject(m, nullptr) : nullptr;
     if (why != nullptr) {
         MPIX_ERR("reducing receive from rank %d, tag %d fails with "
                  "MPI_ERR_TYPE: %s", m.src, m.d.tag, why);
         m.kind_mismatch = true;
     } else if ((op->strided || (m.d.flags & DESCF_STRIDED)) &&
-               op->buf_is_device) {
+               op->buf_is_device && !empty_ok) {
         fail_kind_mismatch(m);
     } else if (m.got > 0 && !m.heap.empty()) {
         /* host message: move already-buffered bytes (message order) into
          * the user buffer */
         uint64_t n = m.got;
         if (n > op->bytes) n = op->bytes;
-        if (n > 0 && op->reduce)
+        if (n > 0 && op->reduce && op->strided)
+            layout_reduce_in(op->buf, op->layout, 0, m.heap.data(), n,
+                             op->red_type, op->red_op);
+        else if (n > 0 && op->reduce)
             /* whole elements: see deliver_chunk */
             reduce_host(op->buf, m.heap.data(),
                         n / reduce_elem_size(op->red_type), op->red_type,
@@ -1127,9 +1170,13 @@ void NativeTransport::deliver_chunk(InboundMsg &m, const Desc &d,
          * holds whole elements except possibly at the message's end, and a
          * message that ends inside an element was rejected in attach.  The
          * receive's own length is a multiple of the element size too, so a
-         * truncated chunk still ends on an element. */
+         * truncated chunk still ends on an element.  Into a strided buffer
+         * the chunk is combined run by run; the runs are whole elements. */
         static_assert(CHUNK_BYTES % 8 == 0, "chunks hold whole elements");
-        if (n > 0 && m.op->reduce)
+        if (n > 0 && m.op->reduce && m.op->strided)
+            layout_reduce_in(m.op->buf, m.op->layout, d.chunk_off, src_chunk,
+                             n, m.op->red_type, m.op->red_op);
+        else if (n > 0 && m.op->reduce)
             reduce_host((char *)m.op->buf + d.chunk_off, src_chunk,
                         n / reduce_elem_size(m.op->red_type), m.op->red_type,
                         m.op->red_op);
@@ -1154,6 +1201,8 @@ void NativeTransport::finish_host_recv(InboundMsg &m)
     if (m.kind_mismatch) {
         st.bytes = 0;
         st.err = MPI_ERR_TYPE;
+    } else if (m.op->reduce && m.op->strided && st.bytes > 0) {
+        g_state->sreduce_host++;
     }
     complete_recv(m.op, st);
     erase_inbound(&m);
@@ -1182,13 +1231,20 @@ const char *NativeTransport::reduce_reject(const InboundMsg &m,
     const Op *op = m.op;
     const uint32_t esize = reduce_elem_size(op->red_type);
     const bool dev_msg = m.d.type == DESC_DEV_NOTIFY;
-    if (m.d.flags & DESCF_STRIDED) return "the sender's message is strided";
+    if ((m.d.flags & DESCF_STRIDED) && !op->reduce_any_sender)
+        return "the sender's message is strided";
     if (m.d.msg_bytes % esize != 0)
         return "the message length is not a multiple of the element size";
     if (dev_msg != op->buf_is_device)
         return "one side is in host memory and the other in device memory";
     if (dev_msg && ((uintptr_t)src % esize) != 0)
         return "the sender's address is not aligned to the element size";
+    /* a strided device sender is walked in place: an element must not
+     * straddle two of its runs (host chunks come in message order) */
+    if (dev_msg && (m.d.flags & DESCF_STRIDED) &&
+        layout_align_bits(m.d.layout, 0) % esize != 0)
+        return "the sender's run or strides are not multiples of the element "
+               "size";
     return nullptr;
 }
 
@@ -1259,13 +1315,26 @@ void NativeTransport::start_dev_copy(InboundMsg &m)
     const uint64_t n = st.bytes;
     const PendingPull pp{op, m.src, m.d.token, st, op->buf, src, n,
                          seen_ns(op, m.d), m.d.partition, 1};
-    /* A reducing receive is always an entry of the reduce kernel, by the
-     * vector or the element path: never hipMemcpyAsync, never a strided
-     * entry.  n is a multiple of the element size (the message's length
-     * is, and a truncated one is cut to the receive's).  A zero-byte
-     * message falls through to the batch of one that copies nothing. */
+    /* A reducing receive is always an entry of a reduce kernel, by the
+     * vector or the element path: never hipMemcpyAsync, never a plain
+     * strided entry.  Strided on either side (reduce_reject let a strided
+     * sender through for the strided reducing calls only) it is an entry of
+     * the strided reduce kernel, layouts as for a plain strided pull.  n is
+     * a multiple of the element size (the message's length is, and a
+     * truncated one is cut to the receive's).  A zero-byte message falls
+     * through to the batch of one that copies nothing. */
     if (op->reduce && n > 0) {
-        pend_reduce_.push_back(PendingReduce{pp, op->red_type, op->red_op});
+        if (strided) {
+            PendingStridedReduce pr{{}, op->red_type, op->red_op};
+            pr.ps.pp = pp;
+            pr.ps.sl = (m.d.flags & DESCF_STRIDED)
+                           ? m.d.layout : layout_contiguous(m.d.msg_bytes);
+            pr.ps.dl = op->strided ? op->layout : layout_contiguous(op->bytes);
+            pend_sreduce_.push_back(pr);
+        } else {
+            pend_reduce_.push_back(
+                PendingReduce{pp, op->red_type, op->red_op});
+        }
         erase_inbound(&m);
         return;
     }
@@ -1506,13 +1575,30 @@ void NativeTransport::flush_strided()
     }
 }
 
+/* The stream of every reducing launch, contiguous or strided: the copy
+ * stream itself, whatever the size.  Should it have been replaced since the
+ * last reducing launch (maybe_switch_prio), the new one waits for the old
+ * one once. */
+hipStream_t NativeTransport::reduce_stream()
+{
+    hipStream_t cs = copy_stream(0);
+    if (reduce_cs_ != nullptr && reduce_cs_ != cs) {
+        hipEvent_t ev = get_event();
+        if (hipEventRecord(ev, reduce_cs_) != hipSuccess ||
+            hipStreamWaitEvent(cs, ev, 0) != hipSuccess)
+            MPIX_ERR("reduce: ordering behind the retired copy stream "
+                     "failed: %s", hipGetErrorString(hipGetLastError()));
+        put_event(ev);
+    }
+    reduce_cs_ = cs;
+    return cs;
+}
+
 /* The reducing pulls of this pass: one k_pull_reduce launch, and another
  * for every entry whose destination overlaps one already planned and for
- * every MPIX_PULL_BATCH entries.  All of them go to the copy stream itself,
- * whatever their size: a later launch must run behind an earlier one that
- * combined into the same bytes (pull_kernels.h on why it then sees them).
- * Should the copy stream have been replaced since the last reduce launch
- * (maybe_switch_prio), the new one waits for the old one once. */
+ * every MPIX_PULL_BATCH entries.  All of them go to reduce_stream(): a later
+ * launch must run behind an earlier one that combined into the same bytes
+ * (pull_kernels.h on why it then sees them). */
 void NativeTransport::flush_reduce()
 {
     while (!pend_reduce_.empty()) {
@@ -1532,16 +1618,7 @@ void NativeTransport::flush_reduce()
             items.push_back(pend_reduce_[i].pp);
         }
         pend_reduce_.erase(pend_reduce_.begin(), pend_reduce_.begin() + n);
-        hipStream_t cs = copy_stream(0);
-        if (reduce_cs_ != nullptr && reduce_cs_ != cs) {
-            hipEvent_t ev = get_event();
-            if (hipEventRecord(ev, reduce_cs_) != hipSuccess ||
-                hipStreamWaitEvent(cs, ev, 0) != hipSuccess)
-                MPIX_ERR("reduce: ordering behind the retired copy stream "
-                         "failed: %s", hipGetErrorString(hipGetLastError()));
-            put_event(ev);
-        }
-        reduce_cs_ = cs;
+        hipStream_t cs = reduce_stream();
         const uint64_t tiles = reduce_total_tiles(rplan_);
         const unsigned blocks = tiles < pull_max_blocks() ? (unsigned)tiles
                                                           : pull_max_blocks();
@@ -1560,6 +1637,84 @@ void NativeTransport::flush_reduce()
             fprintf(stderr, "[mpix trace] reduce pull batch n=%zu entries=%u "
                     "tiles=%lu total=%lu B\n", n, rplan_.n,
                     (unsigned long)tiles, (unsigned long)total);
+    }
+}
+
+/* The strided reducing pulls of this pass, behind the contiguous ones on
+ * the same stream (reduce_stream), so that reducing launches into
+ * overlapping memory always follow each other: one k_pull_strided_reduce
+ * launch, and another for every entry whose destination extent overlaps one
+ * already planned and for every MPIX_STRIDED_BATCH entries. */
+void NativeTransport::flush_strided_reduce()
+{
+    while (!pend_sreduce_.empty()) {
+        StridedReduceSeg segs[MPIX_STRIDED_BATCH];
+        size_t n = pend_sreduce_.size();
+        if (n > MPIX_STRIDED_BATCH) n = MPIX_STRIDED_BATCH;
+        for (size_t i = 0; i < n; i++) {
+            const PendingStridedReduce &pr = pend_sreduce_[i];
+            const PendingStrided &ps = pr.ps;
+            StridedReduceSeg &g = segs[i];
+            g.dst = ps.pp.dst;
+            g.src = ps.pp.csrc;
+            g.bytes = ps.pp.n;
+            g.sl = ps.sl;
+            g.dl = ps.dl;
+            if (ps.parts) {
+                g.parts = ps.pp.k;
+                g.s_part_stride = ps.s_part_stride;
+                g.d_part_stride = ps.d_part_stride;
+            }
+            g.type = pr.type;
+            g.op = pr.op;
+        }
+        n = plan_strided_reduce(segs, n, strided_div64_, &srplan_);
+        if (n == 0) {
+            /* reduce_reject and try_run_fast_path let nothing through that
+             * the planner refuses */
+            MPIX_ERR("strided reduce: a pull that steps in fractions of an "
+                     "element reached the planner");
+            PendingPull pp = pend_sreduce_.front().ps.pp;
+            pend_sreduce_.erase(pend_sreduce_.begin());
+            pp.st.err = MPI_ERR_OTHER;
+            finish_pull(pp, nullptr);
+            continue;
+        }
+        uint64_t total = 0;
+        std::vector<PendingPull> items;
+        for (size_t i = 0; i < n; i++) {
+            total += pend_sreduce_[i].ps.pp.n;
+            items.push_back(pend_sreduce_[i].ps.pp);
+        }
+        pend_sreduce_.erase(pend_sreduce_.begin(), pend_sreduce_.begin() + n);
+        hipStream_t cs = reduce_stream();
+        const uint64_t tiles = strided_reduce_total_tiles(srplan_);
+        /* the limit of the contiguous reducing launches it shares the
+         * stream with (MPIX_PULL_BLOCKS) */
+        const unsigned blocks = tiles < pull_max_blocks() ? (unsigned)tiles
+                                                          : pull_max_blocks();
+        const bool wide = strided_reduce_plan_wide(srplan_);
+        g_state->sreduce_launches++;
+        g_state->sreduce_msgs += pull_ops(items);
+        g_state->sreduce_entries += srplan_.n;
+        /* t_launch_ns stays 0: the batch legs of MPIX_STATS count plain
+         * pulls */
+        if (submit_batch(std::move(items), cs, "k_pull_strided_reduce",
+                         [&](const PullDone *done) {
+                             launch_strided_reduce(srplan_, wide, blocks, cs,
+                                                   done);
+                             return hipGetLastError();
+                         }) == nullptr)
+            continue;
+        if (trace_on()) {
+            unsigned vec = 0; /* entries on the vector path */
+            for (uint32_t i = 0; i < srplan_.n; i++)
+                vec += srplan_.e[i].glog == 4;
+            fprintf(stderr, "[mpix trace] strided reduce pull batch n=%zu "
+                    "entries=%u vec=%u tiles=%lu total=%lu B wide=%d\n", n,
+                    srplan_.n, vec, (unsigned long)tiles,
+                    (unsigned long)total, (int)wide);
+        }
     }
 }
 

@@ -1,9 +1,11 @@
 /* mpix — the pull kernels of the native transport and their launch dispatch.
  * HIP only; included by native.cpp, and by
  * tests/native/pull_kernels_check.hip, which launches every variant in here
- * directly (tests/native/reduce_kernels_check.hip for the reduce kernels).
- * The host plans a batch (pull_plan.h, strided_plan.h, reduce_plan.h); what
- * runs on the device is in here. */
+ * directly (tests/native/reduce_kernels_check.hip for the reduce kernels,
+ * tests/native/strided_reduce_kernels_check.hip for the strided reduce
+ * kernels).  The host plans a batch (pull_plan.h, strided_plan.h,
+ * reduce_plan.h, strided_reduce_plan.h); what runs on the device is in
+ * here. */
 #ifndef MPIX_TRANSPORT_PULL_KERNELS_H
 #define MPIX_TRANSPORT_PULL_KERNELS_H
 
@@ -12,6 +14,7 @@
 #include "pull_plan.h"
 #include "reduce_plan.h"
 #include "strided_plan.h"
+#include "strided_reduce_plan.h"
 
 namespace mpix {
 
@@ -505,6 +508,129 @@ __global__ __launch_bounds__(PULL_THREADS) void k_pull_reduce_done(
     pull_signal_done(d);
 }
 
+/* Strided reducing pull: the walk of k_pull_strided with the combine of
+ * k_pull_reduce (MPIX_Irecv_reduce_strided_enqueue,
+ * MPIX_Precv_init_reduce_strided).  Units are indexed in message space and
+ * decomposed per side by strided_entry_offsets, always with the partition
+ * level (an entry without one has a quotient of 0;
+ * profiles/strided_partitions.md measured no cost for it), every unit
+ * bounds-checked, blocks grid-striding over tile_end[].  Two unit sizes
+ * (strided_reduce_plan.h): 16 bytes, combined by reduce_v4, or one element,
+ * combined by reduce_bits, 16 / size rounds of it per tile.  Per round a
+ * thread issues its U nontemporal loads of the (remote) source, then its U
+ * plain loads of the destination, then combines in registers, then stores.
+ * The plain load of dst sees the user's data by the argument above
+ * k_pull_reduce; no element is touched by two blocks of one launch because
+ * plan_strided_reduce ends the batch before overlapping extents.  Type and
+ * op are per entry and switched on once per tile.  WIDE as in
+ * k_pull_strided.  k_pull_strided_reduce stores nontemporal and signals
+ * nothing; k_pull_strided_reduce_done stores every byte write-through, then
+ * pull_signal_done, with no fence. */
+template <int TYPE, bool VEC> struct StridedRedUnit { typedef RedB<TYPE> U; };
+template <int TYPE> struct StridedRedUnit<TYPE, true> { typedef pull_v4 U; };
+
+template <int TYPE, int OP, bool VEC, bool WIDE, PullStore S>
+static __device__ __forceinline__ void strided_reduce_tile(
+    const StridedEntry &e, uint64_t unit0)
+{
+    typedef typename StridedRedUnit<TYPE, VEC>::U T;
+    typedef const __attribute__((address_space(1))) T *gsrc;
+    typedef __attribute__((address_space(1))) T *gdst;
+    constexpr int U = MPIX_STRIDED_UNROLL;
+    constexpr int ROUNDS = 16 / (int)sizeof(T);
+    constexpr bool wide = WIDE;
+#pragma unroll 1
+    for (int j = 0; j < ROUNDS; j++) {
+        T a[U], b[U];
+        int64_t doff[U];
+        bool ok[U];
+#pragma unroll
+        for (int k = 0; k < U; k++) {
+            const uint64_t u = unit0 +
+                (uint64_t)(j * U + k) * PULL_THREADS + threadIdx.x;
+            ok[k] = u < e.units;
+            if (ok[k]) {
+                int64_t soff;
+                strided_entry_offsets(e, u, wide, true, &soff, &doff[k]);
+                b[k] = __builtin_nontemporal_load((gsrc)(e.src + soff));
+            }
+        }
+#pragma unroll
+        for (int k = 0; k < U; k++)
+            if (ok[k]) a[k] = *(gdst)(e.dst + doff[k]);
+#pragma unroll
+        for (int k = 0; k < U; k++)
+            if (ok[k]) {
+                if constexpr (VEC)
+                    a[k] = reduce_v4<TYPE, OP>(a[k], b[k]);
+                else
+                    a[k] = reduce_bits<TYPE, OP>(a[k], b[k]);
+                pull_st_any<S, T, true>((gdst)(e.dst + doff[k]), a[k]);
+            }
+    }
+}
+
+template <bool WIDE, PullStore S>
+static __device__ __forceinline__ void pull_strided_reduce_body(
+    const StridedReduceTable &t)
+{
+    const uint64_t total = t.tile_end[t.n - 1];
+    uint32_t c = 0;
+    uint64_t first = 0, end = t.tile_end[0];
+    StridedEntry cur = t.e[0];
+    uint32_t sel = t.type[0] * RED_NOPS + t.op[0];
+    for (uint64_t tile = blockIdx.x; tile < total; tile += gridDim.x) {
+        if (tile >= end) {
+            do {
+                first = end;
+                end = t.tile_end[++c];
+            } while (tile >= end);
+            cur = t.e[c];
+            sel = t.type[c] * RED_NOPS + t.op[c];
+        }
+        const uint64_t unit0 = ((tile - first) * MPIX_STRIDED_TILE) >> cur.glog;
+        const bool vec = cur.glog == 4;
+#define STRIDED_REDUCE_OP(TY, OP)                                        \
+    case TY * RED_NOPS + OP:                                             \
+        if (vec)                                                         \
+            strided_reduce_tile<TY, OP, true, WIDE, S>(cur, unit0);      \
+        else                                                             \
+            strided_reduce_tile<TY, OP, false, WIDE, S>(cur, unit0);     \
+        break;
+#define STRIDED_REDUCE_CASE(TY)    \
+    STRIDED_REDUCE_OP(TY, RED_SUM) \
+    STRIDED_REDUCE_OP(TY, RED_MAX) \
+    STRIDED_REDUCE_OP(TY, RED_MIN)
+        switch (sel) {
+            STRIDED_REDUCE_CASE(RED_F32)
+            STRIDED_REDUCE_CASE(RED_F64)
+            STRIDED_REDUCE_CASE(RED_BF16)
+            STRIDED_REDUCE_CASE(RED_F16)
+            STRIDED_REDUCE_CASE(RED_I32)
+            STRIDED_REDUCE_CASE(RED_I64)
+        default: break; /* the host validated type and op */
+        }
+#undef STRIDED_REDUCE_CASE
+#undef STRIDED_REDUCE_OP
+    }
+}
+
+template <bool WIDE>
+__global__ __launch_bounds__(PULL_THREADS) void k_pull_strided_reduce(
+    const StridedReduceTable t)
+{
+    pull_strided_reduce_body<WIDE, PULL_ST_NT>(t);
+}
+
+/* MPIX_PULL_DONE=word: write-through stores, then pull_signal_done */
+template <bool WIDE>
+__global__ __launch_bounds__(PULL_THREADS) void k_pull_strided_reduce_done(
+    const StridedReduceTable t, const PullDone d)
+{
+    pull_strided_reduce_body<WIDE, PULL_ST_WT>(t);
+    pull_signal_done(d);
+}
+
 /* Launch dispatch.  Each variant comes as a pair: the kernel that stores
  * write-through and signals the completion word, launched when `done` is
  * given, and the plain one whose completion is an event or a tail kernel
@@ -567,6 +693,26 @@ static inline void launch_reduce(const ReduceTable &t, unsigned blocks,
     else
         hipLaunchKernelGGL(k_pull_reduce, dim3(blocks), dim3(PULL_THREADS), 0,
                            cs, t);
+}
+
+/* the strided reducing pull: k_pull_strided_reduce_done when `done` is
+ * given, else k_pull_strided_reduce; `wide`: the 64-bit-division pair.  A
+ * template only so that the four kernels (1.6 MB of code, a minute to
+ * compile) are emitted by the files that launch them, not by every file
+ * that includes this header. */
+template <typename Table = StridedReduceTable>
+static inline void launch_strided_reduce(const Table &t,
+                                         bool wide, unsigned blocks,
+                                         hipStream_t cs, const PullDone *done)
+{
+    if (done != nullptr)
+        hipLaunchKernelGGL(wide ? k_pull_strided_reduce_done<true>
+                                : k_pull_strided_reduce_done<false>,
+                           dim3(blocks), dim3(PULL_THREADS), 0, cs, t, *done);
+    else
+        hipLaunchKernelGGL(wide ? k_pull_strided_reduce<true>
+                                : k_pull_strided_reduce<false>,
+                           dim3(blocks), dim3(PULL_THREADS), 0, cs, t);
 }
 
 #undef PULL_KERNELS

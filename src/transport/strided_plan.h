@@ -205,6 +205,37 @@ static inline void strided_side_prepare(const MPIX_Layout &l, uint64_t units,
     }
 }
 
+/* One entry from one segment, walked in units of 1 << glog bytes; the caller
+ * chose glog so that the unit divides layout_granule of the segment. */
+static inline void strided_entry_prepare(const StridedSeg &g, uint32_t glog,
+                                         bool force_wide, StridedEntry *out)
+{
+    StridedEntry &e = *out;
+    const bool parts = g.parts > 1;
+    e.dst = (char *)g.dst;
+    e.src = (const char *)g.src;
+    e.units = g.bytes >> glog;
+    e.glog = glog;
+    e.wide = (force_wide || e.units >= ((uint64_t)1 << 31)) ? 1 : 0;
+    e.part_units = parts ? e.units / g.parts : e.units;
+    e.s_part_stride = parts ? g.s_part_stride : 0;
+    e.d_part_stride = parts ? g.d_part_stride : 0;
+    e.d_part = StridedDiv{0, 0};
+    if (!e.wide) e.d_part = strided_div_prepare((uint32_t)e.part_units);
+    strided_side_prepare(g.sl, e.part_units, glog, e.wide != 0, &e.s);
+    strided_side_prepare(g.dl, e.part_units, glog, e.wide != 0, &e.d);
+}
+
+/* layout_granule of a segment: its part strides count only for a run */
+static inline uint32_t strided_seg_granule(const StridedSeg &g)
+{
+    const bool parts = g.parts > 1;
+    return layout_granule(g.sl, (uint64_t)(uintptr_t)g.src, g.dl,
+                          (uint64_t)(uintptr_t)g.dst,
+                          parts ? g.s_part_stride : 0,
+                          parts ? g.d_part_stride : 0);
+}
+
 /* Plan the first min(n, MPIX_STRIDED_BATCH) entries of `in` into `out`.
  * Returns how many entries were consumed (0 for an empty batch, in which
  * case out->n is 0 and nothing may be launched).  force_wide makes every
@@ -218,26 +249,10 @@ static inline size_t plan_strided(const StridedSeg *in, size_t n,
     if (n > MPIX_STRIDED_BATCH) n = MPIX_STRIDED_BATCH;
     uint64_t tiles = 0;
     for (size_t i = 0; i < n; i++) {
-        StridedEntry &e = out->e[i];
-        const bool parts = in[i].parts > 1;
-        uint32_t g = layout_granule(in[i].sl, (uint64_t)(uintptr_t)in[i].src,
-                                    in[i].dl, (uint64_t)(uintptr_t)in[i].dst,
-                                    parts ? in[i].s_part_stride : 0,
-                                    parts ? in[i].d_part_stride : 0);
+        const uint32_t g = strided_seg_granule(in[i]);
         uint32_t glog = 0;
         while ((1u << glog) < g) glog++;
-        e.dst = (char *)in[i].dst;
-        e.src = (const char *)in[i].src;
-        e.units = in[i].bytes >> glog;
-        e.glog = glog;
-        e.wide = (force_wide || e.units >= ((uint64_t)1 << 31)) ? 1 : 0;
-        e.part_units = parts ? e.units / in[i].parts : e.units;
-        e.s_part_stride = parts ? in[i].s_part_stride : 0;
-        e.d_part_stride = parts ? in[i].d_part_stride : 0;
-        e.d_part = StridedDiv{0, 0};
-        if (!e.wide) e.d_part = strided_div_prepare((uint32_t)e.part_units);
-        strided_side_prepare(in[i].sl, e.part_units, glog, e.wide != 0, &e.s);
-        strided_side_prepare(in[i].dl, e.part_units, glog, e.wide != 0, &e.d);
+        strided_entry_prepare(in[i], glog, force_wide, &out->e[i]);
         uint64_t b = in[i].bytes;
         tiles += b / MPIX_STRIDED_TILE + (b % MPIX_STRIDED_TILE != 0);
         out->tile_end[i] = tiles;
